@@ -1,7 +1,14 @@
 """Headline benchmark: RS8 k=64/m=32, 1400-byte segments, encode + 16-erasure decode, in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline figure needs and no more: it builds the batch, warms up,
+times exactly K steps and prints the line (value, ms_per_step, and the per-kernel times and
+rooflines that the events inside the timed steps give for free).  `--full` adds every leg that
+takes runs of its own: the achievable-copy rates beside the roofline, the host-resident
+(PCIe-inclusive) steps, the clean round-trip check ("verified") and the CPU baseline.
+`--dump-outputs DIR` writes what the last timed step left to a caller (dump_outputs below).
 
 `--gpus N` without a launcher starts N rank processes of this script itself (one per GPU,
 before anything touches the GPU); under a launcher --gpus must equal WORLD_SIZE.  `--dry-run`
@@ -21,8 +28,8 @@ the same formula as the CPU baseline; SURVEY.md 8d's "combined"
 --strong splits a fixed total of --blocks over the ranks instead (norm_amd/dist.py shard).  roofline = the encode kernel's
 algorithmic HBM bytes per launch / its measured launch time vs 8 TB/s, for the step's dominant
 kernel (the longer of the encode, (k+m)*vec per block, and the repair call, (k+e)*vec per block);
-both halves are in the line.  After timing, one clean encode -> erase -> repair round trip from the
-pristine source is compared byte for byte ("verified"; --no-verify skips it).
+both halves are in the line.  With --full, after timing, one clean encode -> erase -> repair round
+trip from the pristine source is compared byte for byte ("verified"; --no-verify skips it).
 """
 import argparse
 import json
@@ -72,8 +79,14 @@ def parse():
     p.add_argument("--share-gpu", action="store_true",
                    help="one-GPU rehearsal of the N-rank path: every rank runs the real workload on cuda:0 and "
                         "the collectives go over gloo (the line says so; never a scaling number)")
-    p.add_argument("--steps", type=int, default=20)
+    p.add_argument("--steps", type=int, default=20, help="timed steps (exactly this many)")
     p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the legs that take runs of their own: achievable-copy "
+                        "rates, host-resident steps, the clean round-trip check and the CPU baseline (the "
+                        "--host-steps, --no-verify, --no-cpu-baseline and --cpu-* options shape these legs)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step left in the batch as DIR/<name>.npy (see dump_outputs)")
     p.add_argument("--blocks", type=int, default=65536,
                    help="FEC blocks per GPU (weak scaling), or in total with --strong")
     p.add_argument("--strong", action="store_true",
@@ -97,7 +110,51 @@ def parse():
     p.add_argument("--host-blocks", type=int, default=0,
                    help="blocks per GPU in the pinned host batch of --host-steps (the first ones of the "
                         "device batch; 0: all of them at N = 1, a quarter per rank at N > 1)")
-    return p.parse_args()
+    a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return a
+
+
+DUMP_BUDGET = 64 * 10**6  # bytes of .npy payload per rank
+DUMP_SEED = 0x44554D50
+
+
+def dump_outputs(path, blocks, status, rank):
+    """What a caller of the timed path holds after the last timed step, as float .npy files:
+
+      blocks_sample.npy        float32 (n, k + m, vec): whole blocks (source, repaired and parity
+                               segments) of a fixed, seeded choice of n blocks of this rank's batch
+      blocks_sample_index.npy  float64 (n,): which blocks those are (sorted)
+      block_sums.npy           float64 (nb,): the sum of every byte of each block, all blocks
+      status.npy               float32 (nb,): decode's per-block return value, all blocks
+
+    The choice depends only on the batch shape, so two builds run with the same arguments write
+    the same blocks.  n is what fits in DUMP_BUDGET beside the per-block arrays (beyond 2^21
+    blocks those two are the same kind of seeded choice).  Ranks above 0 write <name>.rank<r>.npy."""
+    import numpy as np
+    import torch
+
+    nb = blocks.shape[0]
+    os.makedirs(path, exist_ok=True)
+    gen = torch.Generator().manual_seed(DUMP_SEED)
+    perm = torch.randperm(nb, generator=gen)
+    per_block = torch.sort(perm[: 1 << 21]).values if nb > (1 << 21) else None
+    left = DUMP_BUDGET - 12 * min(nb, 1 << 21) - 8 * 128
+    n = max(1, min(nb, left // (blocks[0].numel() * 4 + 8)))
+    idx = torch.sort(perm[:n]).values
+    sums = blocks.view(nb, -1).sum(dim=1, dtype=torch.int64)
+    st = status
+    if per_block is not None:
+        sums, st = sums[per_block.to(blocks.device)], status[per_block.to(blocks.device)]
+    out = {
+        "blocks_sample": blocks[idx.to(blocks.device)].cpu().numpy().astype(np.float32),
+        "blocks_sample_index": idx.numpy().astype(np.float64),
+        "block_sums": sums.cpu().numpy().astype(np.float64),
+        "status": st.cpu().numpy().astype(np.float32),
+    }
+    for name, arr in out.items():
+        np.save(os.path.join(path, name + (f".rank{rank}" if rank else "") + ".npy"), arr)
 
 
 def dry_run(a, world, rank):
@@ -205,7 +262,8 @@ def main():
         if dist is not None:
             dist.barrier()
 
-    orig = None if a.no_verify else blocks[:, :k].clone()
+    verify = a.full and not a.no_verify
+    orig = blocks[:, :k].clone() if verify else None
     for _ in range(a.warmup):
         step()
     torch.cuda.synchronize(dev)
@@ -235,6 +293,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, blocks, status, rank)
+
     # ---- per-kernel durations with HIP events on the launch stream ----
     def timed(fn, n):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -251,23 +312,26 @@ def main():
     # achievable HBM rate on this box (report it beside the 8 TB/s spec): a 4 GiB
     # device-to-device copy by the library's streaming kernel (16 B per lane, non-temporal),
     # read + write bytes over its time; torch's copy_ (the runtime's blit kernel) beside it
-    with torch.cuda.stream(stream):
-        csrc = torch.empty(1 << 32, dtype=torch.uint8, device=dev)
-        cdst = torch.empty_like(csrc)
-        cdst.copy_(csrc)
-    stream_copy(cdst, csrc, stream=stream)
-    copy_ms = timed(lambda: stream_copy(cdst, csrc, stream=stream), 5)
-    def blit():
-        with torch.cuda.stream(stream):  # timed() brackets `stream`: the copy must run on it
+    copy_gbs = blit_gbs = None
+    if a.full:
+        with torch.cuda.stream(stream):
+            csrc = torch.empty(1 << 32, dtype=torch.uint8, device=dev)
+            cdst = torch.empty_like(csrc)
             cdst.copy_(csrc)
+        stream_copy(cdst, csrc, stream=stream)
+        copy_ms = timed(lambda: stream_copy(cdst, csrc, stream=stream), 5)
 
-    blit_ms = timed(blit, 5)
-    copy_gbs = 2 * csrc.numel() / (copy_ms * 1e-3) / 1e9
-    blit_gbs = 2 * csrc.numel() / (blit_ms * 1e-3) / 1e9
-    del csrc, cdst
+        def blit():
+            with torch.cuda.stream(stream):  # timed() brackets `stream`: the copy must run on it
+                cdst.copy_(csrc)
+
+        blit_ms = timed(blit, 5)
+        copy_gbs = 2 * csrc.numel() / (copy_ms * 1e-3) / 1e9
+        blit_gbs = 2 * csrc.numel() / (blit_ms * 1e-3) / 1e9
+        del csrc, cdst
 
     host = None
-    if a.host_steps > 0:
+    if a.full and a.host_steps > 0:
         import numpy as np
 
         # default: the whole batch on one GPU; a quarter per rank when several ranks pin host
@@ -356,7 +420,7 @@ def main():
         del hblocks, hnp
 
     ok = None
-    if not a.no_verify:
+    if verify:
         from norm_amd import zero_erasures
 
         # One clean round trip from the pristine source: encode once, erase, repair once, and
@@ -416,7 +480,7 @@ def main():
         return
 
     cpu = None
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         from oracle import pyoracle as orc
 
         usable, visible = host_cores()
@@ -466,10 +530,11 @@ def main():
             "kernel": encode_kernel_name(k, m, vec),
             "algorithmic_bytes_per_launch": enc_bytes,
             "read_only_frac": round(k * vec * nb / (enc_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-            "achievable_copy": {"GBps": round(copy_gbs, 1), "frac": round(achieved / copy_gbs, 4),
-                                "blit_GBps": round(blit_gbs, 1),
-                                "note": "4 GiB device-to-device copy on this GPU by a streaming kernel "
-                                        "(nfec_util_stream_copy), read + write bytes; blit_GBps: torch copy_"},
+            # measured with --full only
+            "achievable_copy": None if copy_gbs is None else {
+                "GBps": round(copy_gbs, 1), "frac": round(achieved / copy_gbs, 4), "blit_GBps": round(blit_gbs, 1),
+                "note": "4 GiB device-to-device copy on this GPU by a streaming kernel "
+                        "(nfec_util_stream_copy), read + write bytes; blit_GBps: torch copy_"},
             "valu": valu,
         },
         # the other half of the step: the repair (plan + fused repair kernel, one decode call)
@@ -495,6 +560,9 @@ def main():
     out = {key: out[key] for key in ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
                                      "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
                                      "roofline", "roofline_encode", "roofline_decode", "kernels_ms", "cpu_baseline"]}
+    out["full"] = a.full  # False: cpu_baseline, achievable_copy, host_resident and verified were not run
+    if a.dump_outputs:
+        out["dump_outputs"] = a.dump_outputs
     if host is not None:
         out["host_resident"] = host
     if ok is not None:

@@ -7,7 +7,7 @@
 #
 # tasks
 #   suite      pytest -m gpu (the whole GPU suite; PYTEST_K narrows it with a -k expression)
-#   bench      bench.py line, then rocprofv3 --kernel-trace --stats of bench.py --steps 10
+#   bench      bench.py --full line, then rocprofv3 --kernel-trace --stats of a plain bench.py --steps 10
 #   rs16       RS16(400,100) 50-erasure repair per 16k blocks under rocprofv3 kernel traces:
 #              source loss, uniform loss over all k + m segments, shortened batches (numData in
 #              [k/2, k]), accumulate, and vec 1460 (vec % 8 != 0); one JSON line each
@@ -59,9 +59,9 @@ for task in "$@"; do
         tail -n 5 "$O/pytest_gpu.log"
         [ $rc -eq 0 ] || die suite $rc ;;
     bench)
-        timeout -k 10 300 python3 bench.py > "$O/bench.json" 2> "$O/bench.err" || die bench $?
+        timeout -k 10 300 python3 bench.py --full > "$O/bench.json" 2> "$O/bench.err" || die bench $?
         cat "$O/bench.json"
-        prof bench_k "$R/bench.py" --steps 10 --no-cpu-baseline --host-steps 0 > /dev/null || die bench_prof $? ;;
+        prof bench_k "$R/bench.py" --steps 10 > /dev/null || die bench_prof $? ;;
     rs16)
         X=$R/tools/bench_extra.py
         prof rs16_source "$X" --workload rs16 || die rs16_source $?

@@ -1737,7 +1737,11 @@ static int decode_device_impl(nfec_codec* c, const nfec_block_batch* b, const ui
             if ((rc = launch_rs_plan2(p2, s))) return rc;
             const uint32_t* gate = nullptr;
             if (fused) {
-                rc = launch_rs8_fused_decode(c->k, c->m, f, s);
+                // the 3-waves-per-SIMD kernel where it applies (lane-major items, segments up to
+                // 1,664 B, m = 32 or 16; NFEC_FDEC3=0: off), else the 2-waves one
+                static const bool use_fdec3 = diag_knob("NFEC_FDEC3", 1) != 0;
+                rc = use_fdec3 ? launch_rs8_fdec3(c->k, c->m, f, s) : NFEC_ENOTSUP;
+                if (rc == NFEC_ENOTSUP) rc = launch_rs8_fused_decode(c->k, c->m, f, s);
                 if (rc != NFEC_OK) return fail(rc == NFEC_ENOTSUP ? NFEC_EDEVICE : rc, "fused decode launch failed");
                 gate = c->w_gate.p;
             }

@@ -564,6 +564,8 @@ struct FdecArgs {
 };
 int launch_rs8_fused_decode(uint32_t k, uint32_t m, const FdecArgs& a, hipStream_t s);
 bool rs8_fused_decode_covers(uint32_t k, uint32_t m, const FdecArgs& a);
+// the same repair at 3 waves per SIMD (rs8_fdec3.hip); NFEC_ENOTSUP for a batch it does not take
+int launch_rs8_fdec3(uint32_t k, uint32_t m, const FdecArgs& a, hipStream_t s);
 
 // MDP decode planning: per block one-stage coefficient matrix over the surviving slots.
 struct MdpPlanArgs {

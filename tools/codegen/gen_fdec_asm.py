@@ -20,13 +20,21 @@ coefficients are wave-uniform and both stages run back to back in registers:
   * z never leaves the register file: the block's HBM traffic is the 48 + 16 segments read and
     the e repaired segments written.
 
+Two kernels do this.  rs8_fdec_* (gen_fdec_asm.hip) is the layout above at 256 VGPRs (2 waves per
+SIMD).  rs8_fdec3 (the fdec3 section below, written to rs8_fdec3.hip by --fdec3) runs 3 waves per
+SIMD at 168 VGPRs: the load ring lives in LDS, filled by LDS-DMA, and half of z is parked there
+during the solve; it takes the lane-major (64, 32) and (64, 16) batches whose segment is at most
+F3_MAX_VEC bytes, the first family every other batch.
+
 A block qualifies when e <= 16 and the used parity rows are exactly rows 0..e-1 (no parity
 erasures among them: NORM's usual case); the kernel marks the blocks it repaired (rows = 0,
 psel = 0) so the unfused kernels that run after it on the same stream skip them.
 
-Usage: gen_fdec_asm.py OUT.hip [k,m ...]
+Usage: gen_fdec_asm.py OUT.hip [k,m ...]          (norm_amd/csrc/gen_fdec_asm.hip)
+       gen_fdec_asm.py --fdec3 OUT.hip           (norm_amd/csrc/rs8_fdec3.hip)
 """
 import os
+import re
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -77,7 +85,7 @@ def solve_pool():
     return make
 
 
-def all_tables(w):
+def all_tables(w, combo_reg=combo_reg):
     code, regs = [], [{}, {}]
     for g in (0, 1):
         single = [w[2 * t + g] for t in range(4)]
@@ -91,7 +99,7 @@ def all_tables(w):
     return code, regs
 
 
-def snippets(regs):
+def snippets(regs, d_reg=d_reg):
     A, B = regs
     # 64 KiB-aligned table start: in the e = 16 solve a snippet address's low word is the table
     # address's high half packed with the u16 offset (s_pack_*_b32_b16), no extract, no add
@@ -441,7 +449,513 @@ def gen_kernel(k, m, probe=None):
 """
 
 
+# ---- fdec3: the same repair at 168 VGPRs (3 waves per SIMD), source columns through an LDS ring ----
+# Register map, quads P = 0..41 (v4P..v4P+3; bank = index mod 4):
+#   v0, v1            left to the compiler: the lane's DMA offset (16 * lane) and LDS address
+#   P1..P11  b0/b1    M4RM combinations (A in bank 0, B in bank 1)
+#   P12..P15 b0/b1    column set X, P16..P19 column set Y: one holds the column, the other serves as
+#                     its transpose temporaries and then receives the next column from LDS
+#   P0..P31  b2/b3    z rows 8..15 (the rows stage 2 parks in LDS; its d accumulators replace them)
+#   P20..P41 b0/b1 and P32..P41 b2/b3: z rows 0..7 (stay in registers through the solve)
+# LDS: a static region of F3_WAVE_LDS bytes per wave, private to it (no barriers): in stage 1 a ring
+# of F3_NSLOT raw source columns filled by LDS-DMA, a slot being the segment as it lies in memory.
+# 160 KiB per CU / 3 workgroups = 54,613 B; 4 * 13,312 = 53,248 B is the largest multiple of the
+# allocation granule (512 B or 1,280 B) below it that splits four ways into 16-byte multiples.
+# 13,312 B = 8 rows * 8 planes * 4 B * 52 lanes, so l4 <= 52: segments of up to 1,664 B.
+F3_VGPRS = 168
+F3_MAX_VEC = 1664
+F3_SLOT = F3_MAX_VEC
+F3_NSLOT = 8
+F3_WAVE_LDS = F3_SLOT * F3_NSLOT
+F3_LDS_BUDGET = (160 * 1024 // 3) // 1280 * 1280
+F3_IN = [0, 1]
+F3_COMBO_P0, F3_SET_P0, F3_ZLO_P0, F3_ZHI_P0 = 1, 12, 20, 32
+S3_EX, S3_BASE = 52, 54                    # saved EXEC; the block's base address
+F3_PARK = 8 * (F3_MAX_VEC // 32)           # bytes of one parked plane pair: 8 per lane, 52 lanes
+# NFEC_FDEC_VARIANT ids (diagnostic library, with NFEC_FDEC3=0 so that the batch reaches
+# launch_rs8_fused_decode): fdec3's own probes (no solve / DMA, waits and LDS reads only / no DMA)
+F3_PROBES = {10: "nos2", 11: "nos1", 12: "noload"}
+assert 4 * F3_WAVE_LDS <= F3_LDS_BUDGET and F3_WAVE_LDS % 16 == 0
+
+
+def f3_combo(g, a):
+    return 4 * (F3_COMBO_P0 + MULTI.index(a)) + g
+
+
+def f3_set(x):
+    return [4 * (F3_SET_P0 + 4 * x + q) + h for q in range(4) for h in (0, 1)]
+
+
+def f3_d(sl, i):
+    """solve accumulators: in the registers of z row 8 + sl, 16 apart (M0-relative in the snippets)"""
+    return 4 * (4 * sl + i // 2) + 2 + (i & 1)
+
+
+def f3_acc(r, i):
+    if r >= 8:
+        return 4 * (4 * (r - 8) + i // 2) + 2 + (i & 1)
+    j = 8 * r + i
+    if j < 44:
+        return 4 * (F3_ZLO_P0 + j // 2) + (j & 1)
+    j -= 44
+    return 4 * (F3_ZHI_P0 + j // 2) + 2 + (j & 1)
+
+
+F3_BLOCKS = []   # instruction runs that recur (transposes, table builds, ...): candidates for
+#                  a macro of their own in the compact form
+
+
+def f3_blk(lines):
+    if tuple(lines) not in F3_BLOCKS:
+        F3_BLOCKS.append(tuple(lines))
+    return lines
+
+
+def f3_temps(regs):
+    """transpose temporaries out of regs (banks 0 and 1 only), per transpose stage"""
+    def make():
+        avail = {0: [r for r in regs if bank(r) == 0], 1: [r for r in regs if bank(r) == 1]}
+
+        def pick(avoid):
+            return avail[1 if avoid == 0 else 0].pop(0)
+        return pick
+    return make
+
+
+def fdec3_stage1(k, m, probe=None):
+    """z rows 0..15 into f3_acc.  The arithmetic is fdec_asm's; a column comes HBM -> LDS by two
+    buffer_load_dwordx4 ... lds pieces (lanes 0..63 bytes 0..1023, the rest at offset 1024, EXEC
+    widened to the piece's lanes) through a descriptor that starts at the segment and has vec
+    records (0 for a column that is not read), so the range check is the hardware's, per dword:
+    the last piece of a 1,400-byte segment is half inside it and reads nothing past it.  16-byte
+    pieces from 8-byte aligned segments: buffer loads need dword alignment only.
+    Ordering, all within the wave: a slot is read (ds_read_b64) after the counted vmcnt that
+    retires its DMA, and re-armed after the lgkmcnt(0) that returned its reads."""
+    G = generator(k, m)
+    nr = min(NCOLS_PAR, m)
+    ncol = k + nr
+    L = [f"s_mov_b64 s[{S3_EX}:{S3_EX + 1}], exec",
+         f"s_mov_b64 s[{S3_BASE}:{S3_BASE + 1}], %[base]",
+         f"s_mov_b32 s{S_LRS + 3}, 0x00020000", f"s_mov_b32 s{S_SRS + 3}, 0x00020000",
+         f"s_mov_b64 s[{S_EM}:{S_EM + 1}], %[em]"]
+    for i, mk in enumerate(MASKS):
+        L.append(f"s_mov_b32 s{S_MASK + i}, 0x{mk:08x}")
+    L += [f"s_load_dwordx8 s[{S_SLOT}:{S_SLOT + 7}], %[sp], 0x0",
+          f"s_load_dwordx4 s[{S_COEF1}:{S_COEF1 + 3}], %[cp], 0x0"]
+    qoff = [None, "%[q1]", "%[q2]", "%[q3]"]
+
+    def dma(c):
+        if probe == "noload":
+            return []
+        if c < k:
+            out = [f"s_bitcmp1_b64 s[{S_EM}:{S_EM + 1}], {c}", f"s_cselect_b32 s{S_LRS + 2}, 0, %[vec]",
+                   f"s_mul_i32 s{S_COL}, %[ss], {c}"]
+        else:
+            out = [f"s_bitcmp1_b32 %[ps], {c - k}", f"s_cselect_b32 s{S_LRS + 2}, %[vec], 0",
+                   f"s_add_u32 s{S_COL}, %[pk], {c - k}", f"s_mul_i32 s{S_COL}, s{S_COL}, %[ss]"]
+        # (an M0 write needs one wait state before the LDS-DMA that reads it: the EXEC write)
+        out += [f"s_add_u32 s{S_LRS}, s{S3_BASE}, s{S_COL}", f"s_addc_u32 s{S_LRS + 1}, s{S3_BASE + 1}, 0",
+                f"s_add_u32 m0, %[wb], {(c % F3_NSLOT) * F3_SLOT}",
+                "s_mov_b64 exec, %[dm0]",
+                f"buffer_load_dwordx4 %[dma], s[{S_LRS}:{S_LRS + 3}], 0 offen lds",
+                "s_mov_b64 exec, %[dm1]",
+                f"buffer_load_dwordx4 %[dma], s[{S_LRS}:{S_LRS + 3}], 0 offen offset:1024 lds",
+                "s_mov_b64 exec, %[live]"]
+        return out
+
+    def lds_read(c):
+        w = f3_set(c % 2)
+        out = []
+        for q in range(4):
+            if q:
+                out.append(f"v_add_u32 v{w[2 * q]}, {qoff[q]}, %[lds]")
+            addr = f"v{w[2 * q]}" if q else "%[lds]"
+            out.append(f"ds_read_b64 v[{w[2 * q]}:{w[2 * q + 1]}], {addr} offset:{(c % F3_NSLOT) * F3_SLOT}")
+        return out
+
+    for r in range(16):
+        for i in range(8):
+            L.append(f"v_mov_b32 v{f3_acc(r, i)}, 0")
+    issued = -1
+    for c in range(min(F3_NSLOT, ncol)):
+        L += dma(c)
+        issued = c
+    L.append("s_mov_b64 exec, %[live]")
+    if probe != "noload":
+        L.append(f"s_waitcnt vmcnt({2 * issued})")
+    L += lds_read(0)
+    for c in range(ncol):
+        w, other = f3_set(c % 2), f3_set((c + 1) % 2)
+        L.append("s_waitcnt lgkmcnt(0)")  # column c is in its set (and slot c % F3_NSLOT is free)
+        if c + F3_NSLOT < ncol:
+            L += dma(c + F3_NSLOT)
+            issued = c + F3_NSLOT
+        if probe != "noload" and c + 1 < ncol:
+            L.append(f"s_waitcnt vmcnt({2 * (issued - c - 1)})")
+        skip = ([f"s_bitcmp1_b64 s[{S_EM}:{S_EM + 1}], {c}"] if c < k else [f"s_bitcmp0_b32 %[ps], {c - k}"])
+        ups, pre = [], []
+        if probe == "nos1":
+            ups = [f"v_xor_b32 v{f3_acc(8, i)}, v{w[i]}, v{f3_acc(8, i)}" for i in range(8)]
+        elif c < k:
+            pre = f3_blk(transpose(w, f3_temps(other)))
+            need = [set(), set()]
+            todo = []
+            for r in range(nr):
+                mat = bitmatrix_rows(G[r][c])
+                for i in range(8):
+                    a, b = split(mat[i])
+                    todo.append((f3_acc(r, i), a, b))
+                    if a:
+                        need[0].add(a)
+                    if b:
+                        need[1].add(b)
+            pre += f3_blk(table_code(w, need, f3_combo))
+            A, B = need
+            for acc, a, b in todo:
+                if a and b:
+                    ups.append(f"v_bitop3_b32 v{acc}, v{acc}, v{A[a]}, v{B[b]} bitop3:0x96")
+                elif a:
+                    ups.append(f"v_xor_b32 v{acc}, v{A[a]}, v{acc}")
+                elif b:
+                    ups.append(f"v_xor_b32 v{acc}, v{B[b]}, v{acc}")
+        else:
+            pre = f3_blk(transpose(w, f3_temps(other)))
+            ups = [f"v_xor_b32 v{f3_acc(c - k, i)}, v{w[i]}, v{f3_acc(c - k, i)}" for i in range(8)]
+        if probe != "nos1":
+            L += skip + [f"s_cbranch_scc1 Lrd{c}_%="]
+        L += pre
+        L.append(f"Lrd{c}_%=:")
+        # the other set's transpose temporaries are dead: it takes the next column during the updates
+        if c + 1 < ncol:
+            L += lds_read(c + 1)
+        if probe != "nos1":
+            L += skip + [f"s_cbranch_scc1 Lskip{c}_%="]
+        L += ups
+        L.append(f"Lskip{c}_%=:")
+    return L
+
+
+def fdec3_stage2(e16, probe=None):
+    """fdec_asm's solve with z rows 8..15 parked in the wave's LDS region (the ring is dead: every
+    DMA retired, every read returned) and the d accumulators in their registers.  Row t's planes
+    reach the window by v_mov, from the row's registers (t < 8) or from the staging set, which a
+    parked row's four ds_read_b64 fill one row ahead, behind the previous row's calls.  The store
+    offsets are recomputed per half; the store descriptor starts at the output's segment and has
+    vec records, so items past the segment are dropped by the range check."""
+    win, stg = f3_set(0), f3_set(1)
+    so = [f3_combo(0, a) for a in MULTI[:4]]
+    free = [f3_combo(g, a) for a in MULTI for g in (0, 1) if f3_combo(g, a) not in so]
+    regs = all_tables(win, f3_combo)[1]
+    cbuf = [S_COEF1, S_COEF2]
+
+    def pool():
+        avail = list(free)
+        return lambda avoid: avail.pop(0)
+
+    S = ["s_cmp_le_u32 %[tmax], 8", "s_cbranch_scc1 Lnopark_%="]
+    for r in range(8, 16):
+        for j in range(4):
+            S.append(f"ds_write_b64 %[lds], v[{f3_acc(r, 2 * j)}:{f3_acc(r, 2 * j + 1)}] offset:{(4 * (r - 8) + j) * F3_PARK}")
+    S += ["s_waitcnt lgkmcnt(0)", "Lnopark_%=:", f"s_mov_b32 s{S_SRS + 2}, %[vec]",
+          f"s_getpc_b64 s[{S_TAB}:{S_TAB + 1}]", "Lpc_%=:",
+          f"s_add_u32 s{S_TAB}, s{S_TAB}, Lsnip0_%=-Lpc_%=", f"s_addc_u32 s{S_TAB + 1}, s{S_TAB + 1}, 0"]
+
+    def solve(x, full):
+        """as fdec_asm's stage2(x, full)"""
+        S = []
+        for h in range(2):
+            if h == 1 and not full:
+                S.extend(["s_cmp_le_u32 %[e], 8", "s_cbranch_scc1 Ldone_%="])
+            S.extend(f3_blk([f"v_mov_b32 v{f3_d(sl, i)}, 0" for sl in range(8) for i in range(8)]))
+            for t in range(0 if probe == "nos2" else 16):
+                if not full:
+                    S.extend([f"s_cmp_le_u32 %[tmax], {t}", f"s_cbranch_scc1 Lrows{h}{x}_%="])
+                cur = cbuf[t % 2]
+                S.append("s_waitcnt lgkmcnt(0)")
+                nt = (t + 1) % 16
+                S.append(f"s_load_dwordx4 s[{cbuf[nt % 2]}:{cbuf[nt % 2] + 3}], %[cp], 0x{32 * nt + 16 * h:x}")
+                for i in range(8):
+                    S.append(f"v_mov_b32 v{win[i]}, v{f3_acc(t, i) if t < 8 else stg[i]}")
+                if 8 <= t + 1 < 16:
+                    for q in range(4):
+                        S.append(f"ds_read_b64 v[{stg[2 * q]}:{stg[2 * q + 1]}], %[lds] offset:{(4 * (t - 7) + q) * F3_PARK}")
+                S.extend(f3_blk(all_tables(win, f3_combo)[0]))
+                S.extend([f"s_mov_b32 s{S_T}, 0", f"s_set_gpr_idx_on s{S_T}, gpr_idx(SRC0,DST)"])
+                for sl in range(8):
+                    s = 8 * h + sl
+                    if not full:
+                        S.extend([f"s_cmp_le_u32 %[e], {s}", f"s_cbranch_scc1 Lsend{h}_{t}{x}_%="])
+                    if full:
+                        op = "s_pack_lh_b32_b16" if sl % 2 == 0 else "s_pack_hh_b32_b16"
+                        S.append(f"{op} s{S_TAB + 2}, s{cur + sl // 2}, s{S_TAB}")
+                    else:
+                        S.extend([f"s_bfe_u32 s{S_T}, s{cur + sl // 2}, 0x{(16 << 16) | (16 * (sl % 2)):x}",
+                                  f"s_add_u32 s{S_TAB + 2}, s{S_TAB}, s{S_T}",
+                                  f"s_addc_u32 s{S_TAB + 3}, s{S_TAB + 1}, 0"])
+                    S.extend([f"s_movk_i32 m0, 0x{GPR_MODE | (16 * sl):x}",
+                              f"s_swappc_b64 s[{S_RET}:{S_RET + 1}], s[{S_TAB + 2}:{S_TAB + 3}]"])
+                S.extend([f"Lsend{h}_{t}{x}_%=:", "s_set_gpr_idx_off"])
+            S.append(f"Lrows{h}{x}_%=:")
+            S.append("s_waitcnt lgkmcnt(0)")
+            if h == 0:
+                S.append(f"s_load_dwordx4 s[{S_COEF1}:{S_COEF1 + 3}], %[cp], 0x10")
+            S.append(f"v_subrev_u32 v{so[0]}, %[wb], %[lds]")
+            for q in range(1, 4):
+                S.append(f"v_add_u32 v{so[q]}, %[q{q}], v{so[0]}")
+            for sl in range(8):
+                s = 8 * h + sl
+                if not full:
+                    S.extend([f"s_cmp_le_u32 %[e], {s}",
+                              "s_cbranch_scc1 Ldone_%=" if h == 1 else f"s_cbranch_scc1 Lhalf{h}{x}_%="])
+                w = [f3_d(sl, i) for i in range(8)]
+                S.extend(f3_blk(transpose(w, pool)))
+                S.extend([f"s_bfe_u32 s{S_T}, s{S_SLOT + s // 2}, 0x{(16 << 16) | (16 * (s % 2)):x}",
+                          f"s_mul_i32 s{S_T}, s{S_T}, %[ss]",
+                          f"s_add_u32 s{S_SRS}, s{S3_BASE}, s{S_T}", f"s_addc_u32 s{S_SRS + 1}, s{S3_BASE + 1}, 0",
+                          "s_cmp_eq_u32 %[acc], 0", f"s_cbranch_scc1 Lna{s}{x}_%="])
+                for q in range(4):
+                    S.append(f"buffer_load_dwordx2 v[{win[2 * q]}:{win[2 * q + 1]}], v{so[q]}, s[{S_SRS}:{S_SRS + 3}], 0 offen")
+                S.append("s_waitcnt vmcnt(0)")
+                for q in range(4):
+                    S.append(f"v_xor_b32 v{w[2 * q]}, v{win[2 * q]}, v{w[2 * q]}")
+                    S.append(f"v_xor_b32 v{w[2 * q + 1]}, v{win[2 * q + 1]}, v{w[2 * q + 1]}")
+                S.append(f"Lna{s}{x}_%=:")
+                for q in range(4):
+                    S.append(f"buffer_store_dwordx2 v[{w[2 * q]}:{w[2 * q + 1]}], v{so[q]}, s[{S_SRS}:{S_SRS + 3}], 0 offen{SPOL}")
+            if h == 0:
+                S.append(f"Lhalf{h}{x}_%=:")
+        return S
+
+    if e16:
+        S += ["s_cmp_eq_u32 %[e], 16", "s_cbranch_scc0 Lgen_%=",
+              f"s_mov_b32 s{S_TAB + 3}, s{S_TAB + 1}", f"s_and_b32 s{S_T}, s{S_TAB}, 0xffff",
+              f"s_cmp_lg_u32 s{S_T}, 0", "s_cbranch_scc1 Lgen_%="]
+        S += solve("f", True)
+        S += ["s_branch Ldone_%=", "Lgen_%=:"]
+    S += solve("", False)
+    S += ["Ldone_%=:", "s_waitcnt lgkmcnt(0)", f"s_mov_b64 exec, s[{S3_EX}:{S3_EX + 1}]", "s_branch Lend_%="]
+    S += snippets(regs, f3_d)
+    S.append("Lend_%=:")
+    return S
+
+
+# The fdec3 source is committed in a compact form: an instruction of one of these shapes is
+# written as a call of a preprocessor macro that expands to its text, several to a line (the
+# straight-line body is 26k instructions; as plain strings it is 1.6 MB).  {i}: a number.
+F3_FORMS = [
+    ("B", "v_bitop3_b32 v{0}, v{0}, v{1}, v{2} bitop3:0x96"),
+    ("S", "v_bitop3_b32 v{0}, s{1}, v{2}, v{0} bitop3:0xca"),
+    ("X", "v_xor_b32 v{0}, v{1}, v{2}"),
+    ("R", "v_lshrrev_b32 v{0}, {1}, v{2}"),
+    ("L", "v_lshlrev_b32 v{0}, {1}, v{2}"),
+    ("M", "v_mov_b32 v{0}, v{1}"),
+    ("Z", "v_mov_b32 v{0}, 0"),
+    ("MK", "s_movk_i32 m0, {0}"),
+    ("SW", f"s_swappc_b64 s[{S_RET}:{S_RET + 1}], s[{S_TAB + 2}:{S_TAB + 3}]"),
+    ("RT", f"s_setpc_b64 s[{S_RET}:{S_RET + 1}]"),
+    ("AC", "s_addc_u32 s{0}, s{1}, 0"),
+    ("AD", "s_add_u32 s{0}, s{1}, s{2}"),
+    ("BF", "s_bfe_u32 s{0}, s{1}, {2}"),
+    ("CE", "s_cmp_le_u32 %[e], {0}"),
+    ("PA", ".p2align {0}"),
+    ("PL", "s_pack_lh_b32_b16 s{0}, s{1}, s{2}"),
+    ("PH", "s_pack_hh_b32_b16 s{0}, s{1}, s{2}"),
+    ("DR", "ds_read_b64 v[{0}:{1}], v{2} offset:{3}"),
+    ("DL", "ds_read_b64 v[{0}:{1}], %[lds] offset:{2}"),
+    ("VA", "v_add_u32 v{0}, %[q{1}], %[lds]"),
+    ("WL", "s_waitcnt lgkmcnt({0})"),
+    ("WV", "s_waitcnt vmcnt({0})"),
+    ("BL", f"buffer_load_dwordx2 v[{{0}}:{{1}}], v{{2}}, s[{S_SRS}:{S_SRS + 3}], 0 offen"),
+    ("BS", f"buffer_store_dwordx2 v[{{0}}:{{1}}], v{{2}}, s[{S_SRS}:{S_SRS + 3}], 0 offen"),
+]
+
+
+def f3_form_nargs(fmt):
+    return 1 + max([int(x) for x in re.findall(r"\{(\d)\}", fmt)], default=-1)
+
+
+def f3_defines():
+    out = []
+    for name, fmt in F3_FORMS:
+        n = f3_form_nargs(fmt)
+        text = '"' + re.sub(r"\{(\d)\}", lambda mt: '" #' + "abcd"[int(mt.group(1))] + ' "', fmt) + '\\n"'
+        text = text.replace(' ""', "").replace('"" ', "")
+        args = "(" + ", ".join("abcd"[:n]) + ")" if n else ""
+        out.append(f"#define {name}{args} {text}")
+    # U<r>: the eight updates of z row r (accumulators fixed), arguments: the A and B entry of each
+    prm = "abcdefghijklmnop"
+    for r in range(16):
+        out.append(f"#define U{r}({', '.join(prm)}) " +
+                   " ".join(f"B({f3_acc(r, i)}, {prm[2 * i]}, {prm[2 * i + 1]})" for i in range(8)))
+    return out
+
+
+def f3_compact(lines, width=200):
+    """-> (defines, body): the asm lines as macro calls and string literals, packed into source
+    lines; a registered run of instructions that occurs more than once becomes a macro K<n>"""
+    lines = list(lines)
+    defs = []
+    for blk in sorted(F3_BLOCKS, key=len, reverse=True):
+        n = len(blk)
+        hits = [i for i in range(len(lines) - n + 1) if lines[i] == blk[0] and tuple(lines[i:i + n]) == blk]
+        if len(hits) < 2 or n < 8:
+            continue
+        name = f"K{len(defs)}"
+        defs.append(f"#define {name} \\\n    " + " \\\n    ".join(f3_compact_lines(blk, width)))
+        for i in reversed(hits):
+            lines[i:i + n] = [f"\0{name}"]
+    return defs, f3_compact_lines(lines, width)
+
+
+def f3_compact_lines(lines, width):
+    pats = []
+    for name, fmt in F3_FORMS:
+        seen, rx = set(), ""
+        for part in re.split(r"(\{\d\})", fmt):
+            if re.fullmatch(r"\{\d\}", part):
+                rx += f"(?P=a{part[1]})" if part in seen else f"(?P<a{part[1]}>0x[0-9a-f]+|[0-9]+)"
+                seen.add(part)
+            else:
+                rx += re.escape(part)
+        pats.append((name, fmt, re.compile(rx)))
+    toks = []
+    for ln in lines:
+        if ln.startswith("\0"):
+            toks.append(ln[1:])
+            continue
+        for name, fmt, rx in pats:
+            mt = rx.fullmatch(ln)
+            if mt:
+                n = f3_form_nargs(fmt)
+                args = [mt.group(f"a{i}") for i in range(n)]
+                assert fmt.format(*args) == ln
+                toks.append(name + ("(" + ",".join(args) + ")" if n else ""))
+                break
+        else:
+            assert '"' not in ln and "\\" not in ln
+            toks.append(f'"{ln}\\n"')
+    rows = {tuple(str(f3_acc(r, i)) for i in range(8)): r for r in range(16)}
+    i = 0
+    while i + 8 <= len(toks):
+        run = [re.fullmatch(r"B\((\d+),(\d+),(\d+)\)", t) for t in toks[i:i + 8]]
+        r = rows.get(tuple(mt.group(1) for mt in run)) if all(run) else None
+        if r is None:
+            i += 1
+            continue
+        toks[i:i + 8] = [f"U{r}(" + ",".join(f"{mt.group(2)},{mt.group(3)}" for mt in run) + ")"]
+        i += 1
+    out, cur = [], ""
+    for t in toks:
+        if cur and len(cur) + 1 + len(t) > width:
+            out.append(cur)
+            cur = ""
+        cur += (" " if cur else "") + t
+    out.append(cur)
+    return out
+
+
+def f3_clobbers():
+    v = [f'"v{i}"' for i in range(F3_VGPRS) if i not in F3_IN]
+    s = [f'"s{i}"' for i in range(S3_EX, 96)]
+    return ", ".join(v + s + ['"m0"', '"scc"', '"memory"'])
+
+
+def gen_kernel3(k, m, probe=None, compact=False):
+    """the fdec3 kernel of (k, m), or one of its timing probes (diagnostic library; their
+    outputs are wrong on purpose)"""
+    K = f"rs8_fdec3_k{k}_m{m}" + (f"_probe_{probe}" if probe else "")
+    nr = min(NCOLS_PAR, m)
+    asm = fdec3_stage1(k, m, None if probe == "nos2" else probe) + fdec3_stage2(nr == 16, probe)
+    if compact:
+        defs, packed = f3_compact(asm)
+        body = "\n        ".join(packed)
+    else:
+        body = '"' + "\\n\"\n        \"".join(asm) + '\\n"'
+    return ("\n".join(defs) + "\n" if compact else "") + f"""__global__ __launch_bounds__(256, 3) void {K}(FdecArgs a)
+{{
+    __shared__ __attribute__((aligned(16))) uint8_t ring[4 * {F3_WAVE_LDS}];
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t blk = blockIdx.x * 4 + wave;
+    if (blk >= a.nblocks) return;
+    const int32_t rows = (int32_t)__builtin_amdgcn_readfirstlane((uint32_t)a.rows[blk]);
+    const uint32_t ps0 = __builtin_amdgcn_readfirstlane(a.psel[2 * (uint64_t)blk]);
+    const uint32_t ps1 = __builtin_amdgcn_readfirstlane(a.psel[2 * (uint64_t)blk + 1]);
+    if (rows <= 0 || rows > 16 || ps1 != 0 || (ps0 >> {nr}) != 0u) return;
+    const uint32_t e = (uint32_t)rows;
+    const uint32_t tmax = 32u - (uint32_t)__builtin_clz(ps0);
+    const uint64_t em = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(a.emask[2 * (uint64_t)blk]) |
+                        ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(a.emask[2 * (uint64_t)blk + 1]) << 32);
+    const uint32_t pk = a.num_data ? __builtin_amdgcn_readfirstlane((uint32_t)a.num_data[blk]) : {k}u;
+    if (lane == 0) {{
+        a.rows[blk] = 0;
+        a.psel[2 * (uint64_t)blk] = 0;
+    }}
+    // lane-major items (lane_major 2): lane L < l4 holds items q * l4 + L.  All 64 lanes enter the
+    // statement: it narrows EXEC to the l4 live lanes itself and widens it around the DMA pieces
+    // (16 bytes per lane: n16 lanes in all, 64 in the first piece), whose offsets every lane needs
+    const uint32_t l4 = (a.ips + 3u) / 4u;
+    const uint32_t n16 = (a.vec + 15u) / 16u;
+    const uint32_t n1 = n16 > 64u ? n16 - 64u : 1u;
+    const uint64_t live = (1ull << l4) - 1ull;
+    const uint64_t dm0 = n16 >= 64u ? ~0ull : (1ull << n16) - 1ull;
+    const uint64_t dm1 = (1ull << n1) - 1ull;
+    const uint32_t wb = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)ring + wave * {F3_WAVE_LDS}u;
+    const uint32_t dma = lane * 16u;
+    const uint32_t lds = wb + lane * 8u;
+    const uint8_t* base = a.base + (uint64_t)blk * a.block_stride;
+    const uint8_t* cp = a.coef + (uint64_t)blk * a.coef_block_stride;
+    const uint16_t* sp = a.out_slots + (uint64_t)blk * a.slots_stride;
+    asm volatile(
+        {body}
+        :
+        : [base] "s"(base), [em] "s"(em), [cp] "s"(cp), [sp] "s"(sp), [e] "s"(e), [ss] "s"(a.seg_stride),
+          [acc] "s"(a.accumulate), [ps] "s"(ps0), [tmax] "s"(tmax), [pk] "s"(pk), [vec] "s"(a.vec),
+          [live] "s"(live), [dm0] "s"(dm0), [dm1] "s"(dm1), [wb] "s"(wb),
+          [q1] "s"(l4 * 8u), [q2] "s"(l4 * 16u), [q3] "s"(l4 * 24u),
+          [dma] "v"(dma), [lds] "v"(lds)
+        : {f3_clobbers()});
+}}
+"""
+
+
 LPOL = SPOL = ""   # cache-policy suffixes (main: --nt-loads / --nt-stores)
+
+
+def main_fdec3(path):
+    """norm_amd/csrc/rs8_fdec3.hip: the fdec3 kernel in the compact form and its launcher.  One
+    kernel serves (64, 32) and (64, 16): both compute z rows 0..15 and the first 16 generator
+    rows of the two codes are the same (checked here).  (64, 8) stays on rs8_fdec_k64_m8."""
+    k = 64
+    assert [list(r) for r in generator(k, 32)[:16]] == [list(r) for r in generator(k, 16)[:16]]
+    assert fdec3_stage1(k, 32) == fdec3_stage1(k, 16)
+    parts = [
+        "// GENERATED by tools/codegen/gen_fdec_asm.py --fdec3 -- do not edit by hand.",
+        "// Fused RS8 erasure repair at 3 waves per SIMD (168 VGPRs, LDS column ring, z rows 8..15 parked",
+        "// in LDS during the solve; DESIGN.md section 4) for k = 64, m = 32 or 16.  The assembly is written",
+        "// with one macro per instruction shape; each expands to the instruction's text.",
+        '#include "nfec_internal.hpp"',
+        "",
+        "namespace nfec {",
+        "namespace {",
+    ] + f3_defines() + [gen_kernel3(k, 32, compact=True)] + [f"#undef {n}" for n, _ in F3_FORMS] + [f"#undef U{r}" for r in range(16)] + [
+        "}  // namespace",
+        "",
+        "// NFEC_ENOTSUP when the batch is not this kernel's (launch_rs8_fused_decode takes it then): it",
+        "// needs lane-major items and a segment that fits the per-wave LDS region",
+        "int launch_rs8_fdec3(uint32_t k, uint32_t m, const FdecArgs& a, hipStream_t s)",
+        "{",
+        f"    if (k != {k} || (m != 32 && m != 16) || a.lane_major != 2u || a.vec > {F3_MAX_VEC}u ||",
+        "        !rs8_fused_decode_covers(k, m, a))",
+        "        return NFEC_ENOTSUP;",
+        "    if (a.nblocks == 0) return NFEC_OK;",
+        f"    hipLaunchKernelGGL(rs8_fdec3_k{k}_m32, dim3((a.nblocks + 3) / 4), dim3(256), 0, s, a);",
+        "    return hipGetLastError() == hipSuccess ? NFEC_OK : NFEC_EDEVICE;",
+        "}",
+        "",
+        "}  // namespace nfec",
+    ]
+    open(path, "w").write("\n".join(parts) + "\n")
 
 
 def main():
@@ -449,6 +963,8 @@ def main():
     # library, make -C norm_amd diag); the product library ships the default kernels only.
     # --nt-loads / --nt-stores: non-temporal column loads / repaired-row stores (A/B builds)
     global LPOL, SPOL
+    if "--fdec3" in sys.argv:
+        return main_fdec3([a for a in sys.argv if a != "--fdec3"][1])
     diag = "--diag" in sys.argv
     LPOL = " nt" if "--nt-loads" in sys.argv else ""
     SPOL = " nt" if "--nt-stores" in sys.argv else ""
@@ -472,6 +988,8 @@ def main():
         if diag and (k, m) == (64, 32):
             for probe in PROBES.values():
                 parts.append(gen_kernel(k, m, probe))
+            for probe in F3_PROBES.values():
+                parts.append(gen_kernel3(k, m, probe))
     parts.append("}  // namespace")
     parts.append("")
     if diag:
@@ -500,6 +1018,11 @@ def main():
         parts.append(f"    if (k == 64 && m == 32 && fdec_variant() == {v}) {{")
         grid = "std::min((a.nblocks + 3) / 4, 1024u)" if probe == "persist" else "(a.nblocks + 3) / 4"
         parts.append(f"        hipLaunchKernelGGL(rs8_fdec_k64_m32_probe_{probe}, dim3({grid}), dim3(256), 0, s, a);")
+        parts.append("        return hipGetLastError() == hipSuccess ? NFEC_OK : NFEC_EDEVICE;")
+        parts.append("    }")
+    for v, probe in (F3_PROBES.items() if diag else ()):
+        parts.append(f"    if (k == 64 && m == 32 && fdec_variant() == {v} && a.lane_major == 2u && a.vec <= {F3_MAX_VEC}u) {{")
+        parts.append(f"        hipLaunchKernelGGL(rs8_fdec3_k64_m32_probe_{probe}, dim3((a.nblocks + 3) / 4), dim3(256), 0, s, a);")
         parts.append("        return hipGetLastError() == hipSuccess ? NFEC_OK : NFEC_EDEVICE;")
         parts.append("    }")
     for k, m in shapes:

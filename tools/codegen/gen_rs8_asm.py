@@ -123,9 +123,10 @@ def epi_temps():
     return make
 
 
-def table_code(w, need):
+def table_code(w, need, combo_reg=combo_reg):
     """Combination entries needed this column.  Group A = planes (0,2,4,6) = w[0,2,4,6]
-    (bank 0), group B = planes (1,3,5,7) = w[1,3,5,7] (bank 1)."""
+    (bank 0), group B = planes (1,3,5,7) = w[1,3,5,7] (bank 1).  combo_reg: where entry a of
+    group g lives (another register map's, gen_fdec_asm.py fdec3)."""
     code = []
     for g in (0, 1):
         single = [w[2 * t + g] for t in range(4)]

@@ -184,6 +184,9 @@ int nfec_codec_encode_paths(const nfec_codec* codec, uint64_t* counts, uint32_t 
 #define NFEC_DPATH_GENERIC 3      /* Gauss-Jordan plan and table-lookup kernels */
 #define NFEC_DPATH_COUNT 4
 int nfec_codec_decode_paths(const nfec_codec* codec, uint64_t* counts, uint32_t n);
+/* Device batches so far whose last vec % 8 bytes ran on the tail kernels beside the fast kernels
+ * (counts[0] encodes, counts[1] decodes); returns 2, < 0 on error. */
+int nfec_codec_tail_batches(const nfec_codec* codec, uint64_t* counts, uint32_t n);
 /* Copies the m x k parity rows of the systematic generator (row p = generator row k+p),
  * row-major, elements of symbol_bytes each.  MDP: the m x k matrix of the LFSR code for a
  * full block of k source symbols.  bytes must be >= m*k*symbol_bytes. */

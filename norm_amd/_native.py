@@ -134,6 +134,7 @@ _SIGS = {
     "nfec_codec_features": (_I, [_P]),
     "nfec_codec_encode_paths": (_I, [_P, ctypes.POINTER(_U64), _U32]),
     "nfec_codec_decode_paths": (_I, [_P, ctypes.POINTER(_U64), _U32]),
+    "nfec_codec_tail_batches": (_I, [_P, ctypes.POINTER(_U64), _U32]),
     "nfec_codec_get_generator": (_I, [_P, _P, ctypes.c_size_t]),
     "nfec_encode": (_I, [_P, ctypes.POINTER(BlockBatch), _P]),
     "nfec_decode": (_I, [_P, ctypes.POINTER(BlockBatch), _P, _U32, _P, _P, _P]),

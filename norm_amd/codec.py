@@ -194,6 +194,15 @@ class _Codec:
         N.check(min(rc, 0), "nfec_codec_decode_paths")
         return {name: int(cnt[i]) for i, name in enumerate(N.DPATH_NAMES)}
 
+    def tail_batches(self):
+        """Device batches so far whose last vector_size % 8 bytes ran on the tail kernels beside
+        the fast kernels, {"encode": n, "decode": n}."""
+        self._need()
+        cnt = (ctypes.c_uint64 * 2)()
+        rc = N.lib().nfec_codec_tail_batches(self._h, cnt, 2)
+        N.check(min(rc, 0), "nfec_codec_tail_batches")
+        return {"encode": int(cnt[0]), "decode": int(cnt[1])}
+
     def _need(self):
         if not self._h:
             raise RuntimeError("codec not initialised (call Init)")

@@ -15,26 +15,6 @@ namespace nfec {
 
 namespace {
 
-struct Gf8Tables {
-    uint8_t exp[512];
-    uint8_t log[256];
-};
-
-constexpr Gf8Tables make_gf8_tables()
-{
-    Gf8Tables t{};
-    uint32_t v = 1;
-    for (uint32_t i = 0; i < 255; ++i) {
-        t.exp[i] = (uint8_t)v;
-        t.exp[i + 255] = (uint8_t)v;
-        t.log[v] = (uint8_t)i;
-        v <<= 1;
-        if (v & 0x100u) v ^= 0x11du;  // the RS8 field, the tower's base field
-    }
-    t.exp[510] = t.exp[511] = 0;
-    return t;
-}
-
 __constant__ Gf8Tables kGf8Tables = make_gf8_tables();
 
 struct TailConsts {

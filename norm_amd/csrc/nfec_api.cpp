@@ -241,6 +241,8 @@ struct nfec_codec {
     // device-batch encodes per path that took them (NFEC_PATH_*, nfec_codec_encode_paths)
     std::atomic<uint64_t> enc_paths[NFEC_PATH_COUNT] = {};
     std::atomic<uint64_t> dec_paths[NFEC_DPATH_COUNT] = {};  // ... and decodes (NFEC_DPATH_*)
+    // device batches whose last vec % 8 bytes ran on the tail kernels (encodes, decodes)
+    std::atomic<uint64_t> tail_batches[2] = {};
 
     // decode workspace (guarded by mu)
     std::mutex mu;
@@ -1021,14 +1023,13 @@ static int rs16_tmvp1_encode(nfec_codec* c, const nfec_block_batch* b, hipStream
     return leave(NFEC_OK);
 }
 
-// RS8 / MDP encode on the runtime-coefficient kernel (gen_rs8_rt.hip); NFEC_ENOTSUP for layouts
-// it does not take (segment tails: vec % 8 != 0, offsets past 2^31)
-int launch_rt_encode(nfec_codec* c, const nfec_block_batch* b, hipStream_t s)
+// the runtime-coefficient kernel's arguments of an RS8 / MDP batch encode (vec_bytes: the whole
+// vector; the callers split it into the 8-byte pieces and the tail); false: no table
+static bool rt_encode_args(const nfec_codec* c, const nfec_block_batch* b, Rs8RtArgs& a)
 {
-    static const bool use_rt = diag_knob("NFEC_RT", 1) != 0;  // 0: the v_perm kernel (A/B)
-    if (!use_rt || !c->d_rt.p || (c->vec & 7u)) return NFEC_ENOTSUP;
+    if (!c->d_rt.p) return false;
     const bool mdp = c->kind == NFEC_MDP;
-    Rs8RtArgs a;
+    a = Rs8RtArgs();
     a.in_base = static_cast<const uint8_t*>(b->blocks);
     a.in_block_stride = b->block_stride;
     a.in_seg_stride = b->seg_stride;
@@ -1056,12 +1057,47 @@ int launch_rt_encode(nfec_codec* c, const nfec_block_batch* b, hipStream_t s)
         a.out_slot0 = c->k;
         if (mdp) a.tab = c->d_rt.p + (uint64_t)(c->k - 1) * (c->rt_block_bytes / 2);
     }
-    return launch_rs8_rt(a, s);
+    return true;
 }
 
-static int encode_device_impl(nfec_codec* c, const nfec_block_batch* b, hipStream_t s, int& path)
+// the last vec % 8 bytes of an encode whose 8-byte pieces a fast kernel took (kernels_gf8tail.hip)
+static int launch_encode_tail(const Rs8RtArgs& a, uint32_t vec, hipStream_t s)
+{
+    const int rc = launch_rs8_rt_tail(a, vec & ~7u, vec & 7u, s);
+    return rc == NFEC_OK ? NFEC_OK : fail(rc == NFEC_ENOTSUP ? NFEC_EDEVICE : rc, "encode tail launch failed");
+}
+
+// RS8 / MDP encode on the runtime-coefficient kernel (gen_rs8_rt.hip) over the vector's 8-byte
+// pieces, then (vec % 8 != 0, tail set) its last 1-7 bytes on the tail kernel with the same
+// arguments; NFEC_ENOTSUP, before anything is launched, for layouts they do not take (offsets
+// past 2^31, unaligned batches)
+int launch_rt_encode(nfec_codec* c, const nfec_block_batch* b, hipStream_t s, bool& tail)
+{
+    static const bool use_rt = diag_knob("NFEC_RT", 1) != 0;  // 0: the v_perm kernel (A/B)
+    Rs8RtArgs a;
+    if (!use_rt || !rt_encode_args(c, b, a)) return NFEC_ENOTSUP;
+    const uint32_t vec8 = c->vec & ~7u, nt = c->vec & 7u;
+    if (nt && !rs8_rt_tail_covers(a, vec8, nt)) return NFEC_ENOTSUP;
+    if (vec8) {
+        Rs8RtArgs a8 = a;
+        a8.vec_bytes = vec8;
+        const int rc = launch_rs8_rt(a8, s);
+        if (rc != NFEC_OK) return rc;
+    }
+    if (!nt) return NFEC_OK;
+    tail = true;
+    return launch_encode_tail(a, c->vec, s);
+}
+
+static int encode_device_impl(nfec_codec* c, const nfec_block_batch* b, hipStream_t s, int& path, bool& tail)
 {
     const bool acc = b->flags & NFEC_ACCUMULATE;
+    // RS8 / MDP vectors of any length: the fast kernels over the 8-byte pieces (vec8 bytes), the
+    // tail kernel over the last nt bytes from the runtime-coefficient table every such codec has
+    // (tail_ok: it takes this batch; else the batch keeps the kernels that take whole vectors)
+    const uint32_t vec8 = c->vec & ~7u, nt = c->vec & 7u;
+    Rs8RtArgs ta;
+    const bool tail_ok = nt && vec8 && c->kind != NFEC_RS16 && rt_encode_args(c, b, ta) && rs8_rt_tail_covers(ta, vec8, nt);
     if (c->kind == NFEC_RS8 && !force_generic()) {
         // bit-sliced kernel specialised to this (k, m) generator, when one was generated
         bs::EncArgs e;
@@ -1077,10 +1113,17 @@ static int encode_device_impl(nfec_codec* c, const nfec_block_batch* b, hipStrea
         e.nt_store = (bs_flags() >> 1) & 1u;
         // hand-allocated assembly kernels first (NFEC_ASM=0 disables them for A/B runs): the
         // 4-role-wave kernels sharing each column's transpose, then the 2-role kernels
-        if (use_asm() && use_q4()) {
+        if (use_asm() && use_q4() && (!nt || tail_ok)) {
             path = NFEC_PATH_FIXED;
+            e.vec = vec8;
             const int rc = launch_rs8_q4_encode(c->k, c->m, e, s);
-            if (rc != NFEC_ENOTSUP) return rc == NFEC_OK ? NFEC_OK : fail(rc, "q4 encode launch failed");
+            e.vec = c->vec;
+            if (rc != NFEC_ENOTSUP) {
+                if (rc != NFEC_OK) return fail(rc, "q4 encode launch failed");
+                if (!nt) return NFEC_OK;
+                tail = true;
+                return launch_encode_tail(ta, c->vec, s);
+            }
         }
 #ifdef NFEC_DIAG
         if (use_asm()) {
@@ -1096,7 +1139,7 @@ static int encode_device_impl(nfec_codec* c, const nfec_block_batch* b, hipStrea
         // any other shape, and shortened batches (per-block mode: the block's numData columns,
         // parity at slot numData + r): bit-sliced with runtime coefficients
         path = NFEC_PATH_RUNTIME;
-        const int rc = launch_rt_encode(c, b, s);
+        const int rc = launch_rt_encode(c, b, s, tail);
         if (rc != NFEC_ENOTSUP) return rc;
     }
     path = NFEC_PATH_GENERIC;
@@ -1208,10 +1251,17 @@ static int encode_device_impl(nfec_codec* c, const nfec_block_batch* b, hipStrea
         e.accumulate = 0;
         e.xcd_remap = bs_flags() & 1u;
         e.nt_store = (bs_flags() >> 1) & 1u;
-        if (use_q4()) {
+        if (use_q4() && (!nt || tail_ok)) {
             path = NFEC_PATH_FIXED;
+            e.vec = vec8;
             const int rc = launch_mdp_q4_encode(c->k, c->m, e, s);
-            if (rc != NFEC_ENOTSUP) return rc == NFEC_OK ? NFEC_OK : fail(rc, "MDP q4 encode launch failed");
+            e.vec = c->vec;
+            if (rc != NFEC_ENOTSUP) {
+                if (rc != NFEC_OK) return fail(rc, "MDP q4 encode launch failed");
+                if (!nt) return NFEC_OK;
+                tail = true;
+                return launch_encode_tail(ta, c->vec, s);
+            }
         }
 #ifdef NFEC_DIAG
         const int rc = launch_mdp_asm_encode(c->k, c->m, e, s);
@@ -1221,7 +1271,7 @@ static int encode_device_impl(nfec_codec* c, const nfec_block_batch* b, hipStrea
     if (!force_generic()) {
         // other shapes and shortened blocks (the block map of each block length as a table)
         path = NFEC_PATH_RUNTIME;
-        const int rc = launch_rt_encode(c, b, s);
+        const int rc = launch_rt_encode(c, b, s, tail);
         if (rc != NFEC_ENOTSUP) return rc;
     }
     path = NFEC_PATH_GENERIC;
@@ -1250,8 +1300,10 @@ static int encode_device_impl(nfec_codec* c, const nfec_block_batch* b, hipStrea
 int encode_device(nfec_codec* c, const nfec_block_batch* b, hipStream_t s)
 {
     int path = NFEC_PATH_GENERIC;
-    const int rc = encode_device_impl(c, b, s, path);
+    bool tail = false;
+    const int rc = encode_device_impl(c, b, s, path, tail);
     if (rc == NFEC_OK) c->enc_paths[path].fetch_add(1, std::memory_order_relaxed);
+    if (rc == NFEC_OK && tail) c->tail_batches[0].fetch_add(1, std::memory_order_relaxed);
     return rc;
 }
 
@@ -1438,7 +1490,8 @@ static int decode_rs16_tw(nfec_codec* c, const nfec_block_batch* b, const uint16
 // caller_locked: the caller already holds c->mu (nfec_decode_vectors keeps it for the whole
 // per-call decode, staging included)
 static int decode_device_impl(nfec_codec* c, const nfec_block_batch* b, const uint16_t* locs, uint32_t lstride,
-                              const uint16_t* counts, int32_t* status, hipStream_t s, bool caller_locked, int& path)
+                              const uint16_t* counts, int32_t* status, hipStream_t s, bool caller_locked, int& path,
+                              bool& tail)
 {
     if (!locs || !counts) return fail(NFEC_EINVAL, "null erasure arrays");
     const bool acc = b->flags & NFEC_ACCUMULATE;
@@ -1466,7 +1519,14 @@ static int decode_device_impl(nfec_codec* c, const nfec_block_batch* b, const ui
     const bool fast = !rt_first && c->kind == NFEC_RS8 && c->m <= 32 && c->k <= 64 && !force_generic() &&
                       has_bitsliced(c->k, c->m) && bs::offsets_fit(b->block_stride, b->seg_stride);
     static const bool use_rt = diag_knob("NFEC_RT", 1) != 0;
-    const bool rt_dec = use_rt && !fast && c->kind == NFEC_RS8 && (c->vec % 8) == 0 && c->d_rt.p && c->d_lwp.p &&
+    // RS8 / MDP vectors of any length: the bit-sliced repair kernels over the 8-byte pieces (vec8
+    // bytes), the tail kernels (kernels_gf8tail.hip) over the last nt bytes.  They read a column's
+    // tail as 8 aligned bytes inside its slot (tail_layout; nfec.h asks for this layout anyway); a
+    // batch without it keeps the kernels that take whole vectors
+    const uint32_t vec8 = c->vec & ~7u, nt = c->kind == NFEC_RS16 ? 0u : c->vec & 7u;
+    const bool tail_layout = nt && (reinterpret_cast<uintptr_t>(b->blocks) & 7u) == 0 && (b->block_stride & 7u) == 0 &&
+                             (b->seg_stride & 7u) == 0 && (uint64_t)vec8 + 8u <= b->seg_stride;
+    const bool rt_dec = use_rt && !fast && c->kind == NFEC_RS8 && (!nt || tail_layout) && c->d_rt.p && c->d_lwp.p &&
                         !force_generic() &&
                         b->block_stride + (uint64_t)(c->k + c->m) * b->seg_stride + c->vec < (1ull << 31);
     const uint32_t E = std::min(c->k, c->m);
@@ -1484,7 +1544,7 @@ static int decode_device_impl(nfec_codec* c, const nfec_block_batch* b, const ui
         r.out_block_stride = b->block_stride;
         r.out_seg_stride = b->seg_stride;
         r.nblocks = nb;
-        r.vec_bytes = c->vec;
+        r.vec_bytes = vec8;
         r.k = n;                          // columns: the block's survivors, up to k + m
         r.m = std::min(c->k, c->m);       // rows: its erased source
         r.per_block = 1;
@@ -1501,8 +1561,14 @@ static int decode_device_impl(nfec_codec* c, const nfec_block_batch* b, const ui
         r.slot_bound = n;
         return r;
     };
-    const bool mdp_rt = c->kind == NFEC_MDP && use_mdp_rt && (c->vec % 8) == 0 && !force_generic() &&
-                        rs8_rt_covers(mdp_rt_args(static_cast<uint8_t*>(b->blocks), 1));
+    // (the layout is probed before the workspace exists: any non-null table stands in for it, so a
+    // codec's first batch takes the same path as its later ones)
+    auto mdp_rt_layout = [&]() {
+        Rs8RtArgs r = mdp_rt_args(static_cast<uint8_t*>(b->blocks), 1);
+        if (!r.tab) r.tab = c->d_rt.p;
+        return (vec8 == 0 || rs8_rt_covers(r)) && (nt == 0 || rs8_rt_tail_covers(r, vec8, nt));
+    };
+    const bool mdp_rt = c->kind == NFEC_MDP && use_mdp_rt && (!nt || tail_layout) && !force_generic() && mdp_rt_layout();
     path = fast ? NFEC_DPATH_FIXED : (rt_dec || mdp_rt) ? NFEC_DPATH_RUNTIME : NFEC_DPATH_GENERIC;
     const uint32_t rt_np = rs8_rt_passes(std::min(c->k, c->m));  // RS8 repair table passes
     const uint64_t ws_per_block = c->kind == NFEC_MDP ? (mdp_rt ? (uint64_t)mdp_np * n * 16 : (uint64_t)n * c->cs)
@@ -1630,8 +1696,13 @@ static int decode_device_impl(nfec_codec* c, const nfec_block_batch* b, const ui
                 p.coef16 = reinterpret_cast<uint16_t*>(c->w_coef1.p);
                 p.npass16 = mdp_np;
                 if ((rc = launch_mdp_plan(p, s))) return rc;
-                if ((rc = launch_rs8_rt(mdp_rt_args(blocks, nb), s)))
+                if (vec8 && (rc = launch_rs8_rt(mdp_rt_args(blocks, nb), s)))
                     return fail(rc == NFEC_ENOTSUP ? NFEC_EDEVICE : rc, "MDP runtime-coefficient repair launch failed");
+                if (nt) {
+                    if ((rc = launch_rs8_rt_tail(mdp_rt_args(blocks, nb), vec8, nt, s)))
+                        return fail(rc == NFEC_ENOTSUP ? NFEC_EDEVICE : rc, "MDP repair tail launch failed");
+                    tail = true;
+                }
                 continue;
             }
             if ((rc = launch_mdp_plan(p, s))) return rc;
@@ -1708,8 +1779,32 @@ static int decode_device_impl(nfec_codec* c, const nfec_block_batch* b, const ui
             f.block_stride = b->block_stride;
             f.seg_stride = b->seg_stride;
             f.nblocks = nb;
-            f.vec = c->vec;
-            f.ips = c->vec / 8;
+            // segment tails: every kernel of this path over the 8-byte pieces, the tail kernel
+            // (after the plan, before the fused kernel clears rows / psel) over the last nt bytes
+            // of every decodable block
+            Rs8FixedDecTailArgs ft;
+            ft.base = blocks;
+            ft.block_stride = b->block_stride;
+            ft.seg_stride = b->seg_stride;
+            ft.nblocks = nb;
+            ft.k = c->k;
+            ft.m = c->m;
+            ft.num_data = nd;
+            ft.rows = c->w_rows.p;
+            ft.emask = c->w_emask.p;
+            ft.psel = c->w_psel.p;
+            ft.pmap = c->w_pmap.p;
+            ft.out_slots = c->w_oslots.p;
+            ft.slots_stride = c->k;
+            ft.coef2 = c->w_coef2.p;
+            ft.coef_stride = dcs;
+            ft.fused_rows = std::min(16u, c->m);
+            ft.gen = c->d_gen.p;
+            ft.accumulate = acc;
+            const bool split = tail_layout && rs8_fixed_dec_tail_covers(ft, vec8, nt);
+            const uint32_t fvec = split ? vec8 : c->vec;  // what the other kernels take
+            f.vec = fvec;
+            f.ips = fvec / 8;
             f.rows = c->w_rows.p;
             f.psel = c->w_psel.p;
             f.emask = c->w_emask.p;
@@ -1725,7 +1820,7 @@ static int decode_device_impl(nfec_codec* c, const nfec_block_batch* b, const ui
             // (strided loads: 2.16 vs 2.02 ms).  NFEC_FDEC_LANEMAJOR overrides (diagnostic library).
             static const uint32_t lane_major = (uint32_t)diag_knob("NFEC_FDEC_LANEMAJOR", 2, 0, 2);
             f.lane_major = lane_major;
-            const bool fused = use_fused && rs8_fused_decode_covers(c->k, c->m, f);
+            const bool fused = use_fused && fvec && rs8_fused_decode_covers(c->k, c->m, f);
             // gate: the plan writes this pass's generation into w_gate when some block needs the
             // unfused kernels; when the fused kernel ran they skip their whole launch otherwise
             const uint32_t gen = ++c->gate_gen;
@@ -1735,6 +1830,13 @@ static int decode_device_impl(nfec_codec* c, const nfec_block_batch* b, const ui
                 p2.fused_rows = std::min(16u, c->m);  // the inverse of the blocks it takes, by row
             }
             if ((rc = launch_rs_plan2(p2, s))) return rc;
+            if (split) {
+                ft.fused_rows = p2.fused_rows;
+                if ((rc = launch_rs8_fixed_dec_tail(ft, vec8, nt, s)))
+                    return fail(rc == NFEC_ENOTSUP ? NFEC_EDEVICE : rc, "fixed-shape repair tail launch failed");
+                tail = true;
+                if (!fvec) continue;  // no 8-byte piece: the tail kernel repaired the whole vector
+            }
             const uint32_t* gate = nullptr;
             if (fused) {
                 // the 3-waves-per-SIMD kernel where it applies (lane-major items, segments up to
@@ -1750,7 +1852,7 @@ static int decode_device_impl(nfec_codec* c, const nfec_block_batch* b, const ui
             d.block_stride = b->block_stride;
             d.seg_stride = b->seg_stride;
             d.nblocks = nb;
-            d.vec = c->vec;
+            d.vec = fvec;
             d.emask = c->w_emask.p;
             d.psel = c->w_psel.p;
             d.pmap = c->w_pmap.p;
@@ -1781,7 +1883,7 @@ static int decode_device_impl(nfec_codec* c, const nfec_block_batch* b, const ui
                 g2.coef_col_stride = dcs;
                 g2.vtab = c->d_vtab.p;
                 g2.nblocks = nb;
-                g2.vec_bytes = c->vec;
+                g2.vec_bytes = fvec;
                 g2.accumulate = acc;
                 if ((rc = launch_gf8_matmul(g2, false, s))) return rc;
                 continue;
@@ -1802,7 +1904,7 @@ static int decode_device_impl(nfec_codec* c, const nfec_block_batch* b, const ui
             a2.coef_col_stride = dcs;
             a2.vtab = c->d_vtab.p;
             a2.nblocks = nb;
-            a2.vec_bytes = c->vec;
+            a2.vec_bytes = fvec;
             a2.accumulate = acc;
             a2.gate = gate;
             a2.gate_gen = gen;
@@ -1871,7 +1973,7 @@ static int decode_device_impl(nfec_codec* c, const nfec_block_batch* b, const ui
             r.out_block_stride = b->block_stride;
             r.out_seg_stride = b->seg_stride;
             r.nblocks = nb;
-            r.vec_bytes = c->vec;
+            r.vec_bytes = vec8;
             r.k = c->k;
             r.m = E;
             r.per_block = 1;
@@ -1887,13 +1989,18 @@ static int decode_device_impl(nfec_codec* c, const nfec_block_batch* b, const ui
             r.tab_pass_stride = (uint64_t)c->k * 16;
             r.accumulate = acc;
             r.slot_bound = c->k + c->m;
-            if (!rs8_rt_covers(r))
+            if ((vec8 && !rs8_rt_covers(r)) || (nt && !rs8_rt_tail_covers(r, vec8, nt)))
                 return fail(NFEC_ENOTSUP, "runtime-coefficient repair: batch layout past its 2^31 offsets");
             p.lwp = c->d_lwp.p;
             p.lw = c->d_lw.p;
             if ((rc = launch_rs8_plan_rt(p, rt_np, s))) return rc;
-            if ((rc = launch_rs8_rt(r, s)))
+            if (vec8 && (rc = launch_rs8_rt(r, s)))
                 return fail(rc == NFEC_ENOTSUP ? NFEC_EDEVICE : rc, "runtime-coefficient repair launch failed");
+            if (nt) {
+                if ((rc = launch_rs8_rt_tail(r, vec8, nt, s)))
+                    return fail(rc == NFEC_ENOTSUP ? NFEC_EDEVICE : rc, "runtime-coefficient repair tail launch failed");
+                tail = true;
+            }
             continue;
         }
         if ((rc = launch_rs_plan(p, s))) return rc;
@@ -2033,8 +2140,10 @@ int decode_device(nfec_codec* c, const nfec_block_batch* b, const uint16_t* locs
                   const uint16_t* counts, int32_t* status, hipStream_t s, bool caller_locked = false)
 {
     int path = NFEC_DPATH_GENERIC;
-    const int rc = decode_device_impl(c, b, locs, lstride, counts, status, s, caller_locked, path);
+    bool tail = false;
+    const int rc = decode_device_impl(c, b, locs, lstride, counts, status, s, caller_locked, path, tail);
     if (rc == NFEC_OK) c->dec_paths[path].fetch_add(1, std::memory_order_relaxed);
+    if (rc == NFEC_OK && tail) c->tail_batches[1].fetch_add(1, std::memory_order_relaxed);
     return rc;
 }
 
@@ -2276,6 +2385,17 @@ int nfec_codec_decode_paths(const nfec_codec* c, uint64_t* counts, uint32_t n)
         counts[i] = v;
     }
     return NFEC_DPATH_COUNT;
+}
+
+int nfec_codec_tail_batches(const nfec_codec* c, uint64_t* counts, uint32_t n)
+{
+    if (!c || (!counts && n)) return fail(NFEC_EINVAL, "null argument");
+    for (uint32_t i = 0; i < n; ++i) {
+        uint64_t v = i < 2 ? c->tail_batches[i].load(std::memory_order_relaxed) : 0;
+        for (const auto& st : c->stripes) v += i < 2 ? st->tail_batches[i].load(std::memory_order_relaxed) : 0;
+        counts[i] = v;
+    }
+    return 2;
 }
 
 int nfec_codec_get_generator(const nfec_codec* c, void* host_out, size_t bytes)

@@ -400,7 +400,8 @@ struct Rs8RtArgs {
     uint64_t out_block_stride = 0;
     uint32_t out_seg_stride = 0;
     uint32_t nblocks = 0;
-    uint32_t vec_bytes = 0;              // multiple of 8
+    uint32_t vec_bytes = 0;              // multiple of 8 for launch_rs8_rt; launch_rs8_rt_tail lifts that
+                                         // (it takes the last vec % 8 bytes and ignores this field)
     uint32_t k = 0, m = 0;               // columns / rows (per-block mode: the largest)
     uint32_t per_block = 0;
     const uint16_t* num_data = nullptr;
@@ -439,6 +440,35 @@ bool rs8_rt_covers(const Rs8RtArgs& a);                // launch_rs8_rt would ta
 // round_up(2m, 4) bytes, padded by 4 columns + 128 bytes
 std::vector<uint16_t> rs8_rt_table(const std::vector<uint32_t>& rows, uint32_t k, uint32_t m);
 inline uint32_t rs8_rt_col_stride(uint32_t m) { return (2u * m + 3u) & ~3u; }
+// the segment tails of the same products (kernels_gf8tail.hip): bytes [off, off + nbytes) of every
+// output row, nbytes 1..7 and off a multiple of 8 (off = vec & ~7: what the 8-byte pieces of
+// launch_rs8_rt leave), with the same arguments, tables (by row, by count, pass-major) and
+// block / column / row rules as launch_rs8_rt; a.vec_bytes, rows_lo / rows_hi are ignored.  Reads a
+// column's tail as 8 bytes at slot + off (strides multiples of 8, off + 8 <= seg stride) and
+// stores exactly nbytes bytes.  NFEC_ENOTSUP (rs8_rt_tail_covers false): nothing was launched.
+int launch_rs8_rt_tail(const Rs8RtArgs& a, uint32_t off, uint32_t nbytes, hipStream_t s);
+bool rs8_rt_tail_covers(const Rs8RtArgs& a, uint32_t off, uint32_t nbytes);
+
+// GF(2^8) log / exp tables of the RS8 field 0x11d (alpha = x), built at compile time for the small
+// log/exp kernels (the segment-tail kernels); exp is doubled so log sums need no reduction
+struct Gf8Tables {
+    uint8_t exp[512];
+    uint8_t log[256];
+};
+constexpr Gf8Tables make_gf8_tables()
+{
+    Gf8Tables t{};
+    uint32_t v = 1;
+    for (uint32_t i = 0; i < 255; ++i) {
+        t.exp[i] = (uint8_t)v;
+        t.exp[i + 255] = (uint8_t)v;
+        t.log[v] = (uint8_t)i;
+        v <<= 1;
+        if (v & 0x100u) v ^= 0x11du;  // the RS8 field, the RS16 tower's base field
+    }
+    t.exp[510] = t.exp[511] = 0;
+    return t;
+}
 
 // RS decode planning (per block): pick parities, invert the e x e system, emit the
 // stage-1 (gather) and stage-2 (inverse) matrices and slot lists.
@@ -566,6 +596,35 @@ int launch_rs8_fused_decode(uint32_t k, uint32_t m, const FdecArgs& a, hipStream
 bool rs8_fused_decode_covers(uint32_t k, uint32_t m, const FdecArgs& a);
 // the same repair at 3 waves per SIMD (rs8_fdec3.hip); NFEC_ENOTSUP for a batch it does not take
 int launch_rs8_fdec3(uint32_t k, uint32_t m, const FdecArgs& a, hipStream_t s);
+
+// The segment tails of the fixed-shape RS8 repair (kernels_gf8tail.hip): bytes [off, off + nbytes)
+// (nbytes 1..7, off a multiple of 8) of every block launch_rs_plan2 found decodable, fused or not,
+// from the plan's outputs in plain bytes: z_p = parity p ^ sum_{j not in emask} G[p][j] d_j for the
+// rows p of psel, d_s = sum_p coef2[row(p)][s] z_p into slot out_slots[s].  coef2 is read as the
+// plan wrote it: by parity row as snippet offsets for the blocks the fused kernel takes
+// (fused_rows, the plan's own rule), by rank (pmap) as bytes otherwise.  Runs after the plan and
+// BEFORE the fused kernel, which clears rows / psel.  k <= 64, m <= 32.
+struct Rs8FixedDecTailArgs {
+    uint8_t* base = nullptr;             // the batch (inputs and outputs in place)
+    uint64_t block_stride = 0;
+    uint32_t seg_stride = 0;
+    uint32_t nblocks = 0;
+    uint32_t k = 0, m = 0;
+    const uint16_t* num_data = nullptr;  // per block (null: k): parity p at slot numData + p
+    const int32_t* rows = nullptr;       // plan outputs
+    const uint32_t* emask = nullptr;
+    const uint32_t* psel = nullptr;
+    const uint8_t* pmap = nullptr;
+    const uint16_t* out_slots = nullptr; // [b][slots_stride]
+    uint32_t slots_stride = 0;
+    const uint8_t* coef2 = nullptr;      // [b][coef_stride][coef_stride]
+    uint32_t coef_stride = 0;
+    uint32_t fused_rows = 0;             // as given to the plan
+    const uint8_t* gen = nullptr;        // m x k generator parity rows, row-major (device)
+    uint32_t accumulate = 0;
+};
+int launch_rs8_fixed_dec_tail(const Rs8FixedDecTailArgs& a, uint32_t off, uint32_t nbytes, hipStream_t s);
+bool rs8_fixed_dec_tail_covers(const Rs8FixedDecTailArgs& a, uint32_t off, uint32_t nbytes);
 
 // MDP decode planning: per block one-stage coefficient matrix over the surviving slots.
 struct MdpPlanArgs {

@@ -212,6 +212,62 @@ int nfec_decode(nfec_codec* codec, const nfec_block_batch* batch, const uint16_t
                 uint32_t erasure_stride, const uint16_t* erasure_counts, int32_t* status,
                 void* stream);
 
+/* ---- receiver assembly on the device ----
+ * What NormObject::HandleObjectMessage does between a NORM_DATA arrival and the Decode call
+ * (normObject.cpp:1548-1644) for a receiver whose segments are already in HBM: put each received
+ * segment into its (block, slot) of a device batch, keep NORM's per-block reception mask, and
+ * build the erasure lists Decode takes from that mask.  The wire layer (nfec_payload_id_read,
+ * nfec_fti_read) gives (block, symbol) per segment on the host; only those descriptors are
+ * uploaded.  All device entries are asynchronous on stream, like nfec_decode, and run on the
+ * codec device that holds the batch (nfec_rx_erasures: the mask).
+ *
+ * A reception mask is uint32_t received[nblocks][mask_stride] in device memory, mask_stride >=
+ * (k + m + 31) / 32: bit s % 32 of word s / 32 is set when slot s of the block holds a received
+ * segment.  The caller zeroes it once.  Bits at or past numData_b + m are ignored everywhere. */
+typedef struct nfec_rx_segments {
+    const void*     payloads;     /* device: received payload bytes, any byte alignment      */
+    const uint64_t* offsets;      /* device [count]: byte offset of segment i in payloads    */
+    const uint32_t* block_index;  /* device [count]: block of the batch                      */
+    const uint16_t* symbol_id;    /* device [count]: slot (source < numData_b <= parity)     */
+    const uint16_t* length;       /* device [count]: payload bytes, <= vector_size           */
+    uint32_t count;
+} nfec_rx_segments;
+
+/* Places segment i into block b = block_index[i], slot s = symbol_id[i] of the batch.  With
+ * nd_b = batch->num_data ? num_data[b] : k, a segment is rejected when b >= nblocks, nd_b is
+ * outside [1, k], s >= nd_b + m or length[i] > vector_size.  Otherwise the slot is claimed by one
+ * atomic OR on its mask word: when the bit was set already the segment is a duplicate and is
+ * dropped (NORM's IsPending test at the top of HandleObjectMessage, race-free: exactly one of
+ * several copies, within one call or across calls, wins the slot); when it was clear the segment
+ * is placed: the slot's first length[i] bytes become the payload, bytes [length[i], vector_size)
+ * zero (the reference's zero pad of a short last or stream segment).  Bytes [vector_size,
+ * seg_stride) of a slot are never written; a rejected or duplicate segment writes no slot and no
+ * mask word.  stats (device [3], may be NULL; the caller zeroes it): the placed, duplicate and
+ * rejected counts are added to stats[0..2].  batch->flags is ignored. */
+int nfec_rx_place(const nfec_codec* codec, const nfec_block_batch* batch, const nfec_rx_segments* segments,
+                  uint32_t* received, uint32_t mask_stride, uint32_t* stats, void* stream);
+/* The erasure lists nfec_decode takes, from reception masks, as NormObject builds them
+ * (normObject.cpp:1560-1606): a block with no source slot of [0, nd_b) missing gets count 0 and
+ * nothing listed (not even missing parity); otherwise every missing source slot ascending, then
+ * every missing parity slot of [nd_b, nd_b + m) ascending.  erasure_counts[b] is the full number
+ * even past erasure_stride (nfec_decode answers status 0 for it); only the first erasure_stride
+ * entries are written.  A block whose nd_b is outside [1, k] gets count 0.  num_data: device
+ * [nblocks] or NULL (= k). */
+int nfec_rx_erasures(const nfec_codec* codec, const uint32_t* received, uint32_t mask_stride,
+                     const uint16_t* num_data, uint32_t nblocks, uint16_t* erasure_locs,
+                     uint32_t erasure_stride, uint16_t* erasure_counts, void* stream);
+/* nfec_rx_erasures into lists the codec owns (stride m, part of the decode workspace: the
+ * ordering rule of nfec_decode holds), then nfec_decode on them.  batch->flags and status as
+ * nfec_decode; the mask is only read.  Counted by nfec_codec_decode_paths like nfec_decode. */
+int nfec_decode_received(nfec_codec* codec, const nfec_block_batch* batch, const uint32_t* received,
+                         uint32_t mask_stride, int32_t* status, void* stream);
+/* nfec_rx_erasures' rule on host arrays, for callers of nfec_decode_host_vectors who hold NORM's
+ * mask: no codec, no GPU.  NFEC_EINVAL for null arrays, k or m of 0, k + m > 65536 or a
+ * mask_stride below (k + m + 31) / 32. */
+int nfec_rx_erasures_host(uint32_t k, uint32_t m, const uint32_t* received, uint32_t mask_stride,
+                          const uint16_t* num_data, uint32_t nblocks, uint16_t* erasure_locs,
+                          uint32_t erasure_stride, uint16_t* erasure_counts);
+
 /* ---- host-resident batched path: same layouts, host pointers (pageable or pinned).
  * Staged through pinned buffers with H2D / compute / D2H overlapped on streams.
  * Synchronous: returns when all outputs are back in host memory.  A codec owns one staging

@@ -48,6 +48,18 @@ class BlockBatch(ctypes.Structure):
     ]
 
 
+class RxSegments(ctypes.Structure):
+    """nfec_rx_segments: received segments in arrival order (device arrays)."""
+    _fields_ = [
+        ("payloads", ctypes.c_void_p),
+        ("offsets", ctypes.c_void_p),
+        ("block_index", ctypes.c_void_p),
+        ("symbol_id", ctypes.c_void_p),
+        ("length", ctypes.c_void_p),
+        ("count", ctypes.c_uint32),
+    ]
+
+
 class CodecInfo(ctypes.Structure):
     _fields_ = [
         ("kind", ctypes.c_int32),
@@ -138,6 +150,10 @@ _SIGS = {
     "nfec_codec_get_generator": (_I, [_P, _P, ctypes.c_size_t]),
     "nfec_encode": (_I, [_P, ctypes.POINTER(BlockBatch), _P]),
     "nfec_decode": (_I, [_P, ctypes.POINTER(BlockBatch), _P, _U32, _P, _P, _P]),
+    "nfec_rx_place": (_I, [_P, ctypes.POINTER(BlockBatch), ctypes.POINTER(RxSegments), _P, _U32, _P, _P]),
+    "nfec_rx_erasures": (_I, [_P, _P, _U32, _P, _U32, _P, _U32, _P, _P]),
+    "nfec_decode_received": (_I, [_P, ctypes.POINTER(BlockBatch), _P, _U32, _P, _P]),
+    "nfec_rx_erasures_host": (_I, [_U32, _U32, _P, _U32, _P, _U32, _P, _U32, _P]),
     "nfec_encode_host": (_I, [_P, ctypes.POINTER(BlockBatch)]),
     "nfec_decode_host": (_I, [_P, ctypes.POINTER(BlockBatch), _P, _U32, _P, _P]),
     "nfec_encode_host_vectors": (_I, [_P, _P, _U32, _P, _U32]),

@@ -203,6 +203,56 @@ class _Codec:
         N.check(min(rc, 0), "nfec_codec_tail_batches")
         return {"encode": int(cnt[0]), "decode": int(cnt[1])}
 
+    # -- receiver assembly on the device (nfec.h, "receiver assembly on the device") --
+    def place_segments(self, blocks, received, payloads, offsets, block_index, symbol_id, length, num_data=None,
+                       stats=None, stream=None):
+        """Put received segments into their (block, slot) of a device batch (nfec_rx_place).
+        received: the batch's reception mask (received_mask()); payloads: uint8 tensor holding the
+        payload bytes; per segment i (all CUDA tensors of one length): offsets int64 (byte offset
+        of its payload), block_index int32, symbol_id int16/uint16, length int16/uint16 (payload
+        bytes, the rest of the slot up to vector_size becomes zero).  stats: int32 [3] the placed,
+        duplicate and rejected counts are added to (zero it first), or None."""
+        self._need()
+        b = _batch_struct(blocks, num_data, False)
+        _mask_check(received, blocks.shape[0])
+        count = offsets.numel()
+        for t, size, what in ((offsets, 8, "offsets"), (block_index, 4, "block_index"), (symbol_id, 2, "symbol_id"),
+                              (length, 2, "length")):
+            if t.element_size() != size or t.numel() != count:
+                raise ValueError(f"{what} must hold {count} elements of {size} bytes")
+        if stats is not None and (stats.element_size() != 4 or stats.numel() < 3):
+            raise ValueError("stats must hold three 32-bit counters")
+        seg = N.RxSegments()
+        seg.payloads = payloads.data_ptr() if payloads.numel() else None
+        for name, t in (("offsets", offsets), ("block_index", block_index), ("symbol_id", symbol_id),
+                        ("length", length)):
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous CUDA (HIP) tensor")
+            setattr(seg, name, t.data_ptr())
+        if not payloads.is_cuda or not payloads.is_contiguous():
+            raise ValueError("payloads must be a contiguous CUDA (HIP) tensor")
+        seg.count = count
+        N.check(N.lib().nfec_rx_place(self._h, ctypes.byref(b), ctypes.byref(seg), _tensor_ptr(received, "received"),
+                                      received.shape[1], _tensor_ptr(stats, "stats"), _stream_handle(stream)),
+                "nfec_rx_place")
+
+    def erasures_from_received(self, received, num_data=None, stride=None, stream=None):
+        """The erasure lists decode_blocks takes, from a reception mask (nfec_rx_erasures):
+        (locs int16 [nblocks, stride], counts int16 [nblocks]); stride defaults to numParity.
+        counts holds the full number of erasures even past stride."""
+        import torch
+
+        self._need()
+        _mask_check(received, received.shape[0])
+        nb = received.shape[0]
+        stride = self.npar if stride is None else stride
+        locs = torch.zeros((nb, stride), dtype=torch.int16, device=received.device)
+        counts = torch.zeros(nb, dtype=torch.int16, device=received.device)
+        N.check(N.lib().nfec_rx_erasures(self._h, _tensor_ptr(received, "received"), received.shape[1],
+                                         _tensor_ptr(num_data, "num_data"), nb, _tensor_ptr(locs, "locs"), stride,
+                                         _tensor_ptr(counts, "counts"), _stream_handle(stream)), "nfec_rx_erasures")
+        return locs, counts
+
     def _need(self):
         if not self._h:
             raise RuntimeError("codec not initialised (call Init)")
@@ -300,6 +350,21 @@ class _Decoder(_Codec):
                                  erasure_locs.shape[1], _tensor_ptr(erasure_counts, "erasure_counts"),
                                  _tensor_ptr(status, "status"), _stream_handle(stream))
         N.check(rc, "nfec_decode")
+        return status
+
+    def decode_received(self, blocks, received, num_data=None, status=None, accumulate=False, stream=None):
+        """decode_blocks with the erasure lists taken from the batch's reception mask
+        (nfec_decode_received); returns int32 status [nblocks].  The mask is only read."""
+        import torch
+
+        self._need()
+        _mask_check(received, blocks.shape[0])
+        if status is None:
+            status = torch.empty(blocks.shape[0], dtype=torch.int32, device=blocks.device)
+        b = _batch_struct(blocks, num_data, accumulate)
+        rc = N.lib().nfec_decode_received(self._h, ctypes.byref(b), _tensor_ptr(received, "received"),
+                                          received.shape[1], _tensor_ptr(status, "status"), _stream_handle(stream))
+        N.check(rc, "nfec_decode_received")
         return status
 
     def decode_blocks_host(self, blocks, erasure_locs, erasure_counts, num_data=None, accumulate=False):
@@ -423,6 +488,39 @@ class NormEncoderMDP(_Encoder):
 
 class NormDecoderMDP(_Decoder):
     KIND = N.NFEC_MDP
+
+
+# -- receiver assembly helpers --
+def _mask_check(received, nblocks):
+    if received.dim() != 2 or received.element_size() != 4 or received.shape[0] != nblocks:
+        raise ValueError("received must be a 32-bit tensor [nblocks, mask_stride]")
+
+
+def received_mask(nblocks, k, m, device="cuda"):
+    """A zeroed reception mask for nblocks blocks of k + m slots: int32 [nblocks, (k + m + 31) // 32];
+    bit s % 32 of word s // 32 is set once slot s holds a received segment."""
+    import torch
+
+    return torch.zeros((nblocks, (k + m + 31) // 32), dtype=torch.int32, device=device)
+
+
+def erasures_from_received_host(k, m, received, num_data=None, stride=None):
+    """nfec_rx_erasures_host: erasure lists from reception masks in host memory (no GPU).  received:
+    NumPy 32-bit array [nblocks, mask_stride]; returns (locs uint16 [nblocks, stride], counts uint16
+    [nblocks]); stride defaults to m."""
+    import numpy as np
+
+    mask = np.ascontiguousarray(received).view(np.uint32)
+    if mask.ndim != 2:
+        raise ValueError("received must be a 32-bit array [nblocks, mask_stride]")
+    nb = mask.shape[0]
+    stride = m if stride is None else stride
+    locs = np.zeros((nb, stride), np.uint16)
+    counts = np.zeros(nb, np.uint16)
+    nd = None if num_data is None else np.ascontiguousarray(num_data, dtype=np.uint16)
+    N.check(N.lib().nfec_rx_erasures_host(k, m, mask.ctypes.data, mask.shape[1], None if nd is None else nd.ctypes.data,
+                                          nb, locs.ctypes.data, stride, counts.ctypes.data), "nfec_rx_erasures_host")
+    return locs, counts
 
 
 # -- synthetic workload helpers (device kernels) --

@@ -254,6 +254,7 @@ struct nfec_codec {
     DevBuf<uint16_t> w_tw2;        // RS16 decode stage 2 on the tower kernel: per-block tables
     DevBuf<uint32_t> w_rowoff;     // ... and output row offsets (TwDecTablesArgs)
     uint32_t gate_gen = 0;         // per-pass generation written into w_gate (RsPlan2Args)
+    DevBuf<uint16_t> w_rxlocs, w_rxcounts;  // nfec_decode_received: the lists built from the mask ([b][m], [b])
     // per-call staging (nfec_encode_segment / nfec_decode_vectors, guarded by mu): one device
     // buffer and one pinned mirror of the same layout, and a stream of the codec's own, so a
     // call is one gather, one H2D, the kernels, one D2H and one scatter
@@ -313,6 +314,8 @@ struct nfec_codec {
         w_cols.release();
         w_tw2.release();
         w_rowoff.release();
+        w_rxlocs.release();
+        w_rxcounts.release();
     }
 };
 
@@ -2429,6 +2432,111 @@ int nfec_decode(nfec_codec* codec, const nfec_block_batch* batch, const uint16_t
     DeviceGuard g(codec->device);
     return decode_device(codec, batch, erasure_locs, erasure_stride, erasure_counts, status,
                          static_cast<hipStream_t>(stream));
+}
+
+// ---- receiver assembly on the device (kernels_rx.hip) ----
+// Arguments are checked before the codec's device is: a null array or a short mask is
+// NFEC_EINVAL on any codec, a host-only codec answers NFEC_EDEVICE to well-formed calls.
+static int check_mask(const nfec_codec* c, const uint32_t* received, uint32_t mask_stride)
+{
+    if (!received) return fail(NFEC_EINVAL, "null received mask");
+    if ((uint64_t)mask_stride * 32u < (uint64_t)c->k + c->m)
+        return fail(NFEC_EINVAL, "mask_stride smaller than (k + m + 31) / 32");
+    return NFEC_OK;
+}
+
+int nfec_rx_place(const nfec_codec* codec, const nfec_block_batch* batch, const nfec_rx_segments* seg,
+                  uint32_t* received, uint32_t mask_stride, uint32_t* stats, void* stream)
+{
+    if (!codec || !batch || !seg) return fail(NFEC_EINVAL, "null codec, batch or segments");
+    int rc = check_mask(codec, received, mask_stride);
+    if (rc) return rc;
+    if (seg->count && !seg->payloads) return fail(NFEC_EINVAL, "null segments->payloads");
+    if (seg->count && !seg->offsets) return fail(NFEC_EINVAL, "null segments->offsets");
+    if (seg->count && !seg->block_index) return fail(NFEC_EINVAL, "null segments->block_index");
+    if (seg->count && !seg->symbol_id) return fail(NFEC_EINVAL, "null segments->symbol_id");
+    if (seg->count && !seg->length) return fail(NFEC_EINVAL, "null segments->length");
+    if ((rc = check_batch(codec, batch)) || batch->nblocks == 0 || seg->count == 0) return rc;
+    // (the stripe is only read: its shape and its device)
+    const nfec_codec* c = stripe_for(const_cast<nfec_codec*>(codec), batch->blocks);
+    if (!c) return fail(NFEC_EINVAL, "batch is not on a device of the codec");
+    DeviceGuard g(c->device);
+    RxPlaceArgs a;
+    a.base = static_cast<uint8_t*>(batch->blocks);
+    a.block_stride = batch->block_stride;
+    a.seg_stride = batch->seg_stride;
+    a.nblocks = batch->nblocks;
+    a.num_data = batch->num_data;
+    a.k = c->k;
+    a.m = c->m;
+    a.vec = c->vec;
+    a.payloads = static_cast<const uint8_t*>(seg->payloads);
+    a.offsets = seg->offsets;
+    a.block_index = seg->block_index;
+    a.symbol_id = seg->symbol_id;
+    a.length = seg->length;
+    a.count = seg->count;
+    a.received = received;
+    a.mask_stride = mask_stride;
+    a.stats = stats;
+    return launch_rx_place(a, static_cast<hipStream_t>(stream));
+}
+
+int nfec_rx_erasures(const nfec_codec* codec, const uint32_t* received, uint32_t mask_stride, const uint16_t* num_data,
+                     uint32_t nblocks, uint16_t* erasure_locs, uint32_t erasure_stride, uint16_t* erasure_counts,
+                     void* stream)
+{
+    if (!codec) return fail(NFEC_EINVAL, "null codec");
+    int rc = check_mask(codec, received, mask_stride);
+    if (rc) return rc;
+    if (!erasure_locs && erasure_stride) return fail(NFEC_EINVAL, "null erasure_locs");
+    if (!erasure_counts) return fail(NFEC_EINVAL, "null erasure_counts");
+    if (primary(codec)->host_only) return host_only_fail();
+    if (nblocks == 0) return NFEC_OK;
+    const nfec_codec* c = stripe_for(const_cast<nfec_codec*>(codec), received);
+    if (!c) return fail(NFEC_EINVAL, "received mask is not on a device of the codec");
+    DeviceGuard g(c->device);
+    RxErasureArgs a;
+    a.received = received;
+    a.mask_stride = mask_stride;
+    a.num_data = num_data;
+    a.k = c->k;
+    a.m = c->m;
+    a.nblocks = nblocks;
+    a.locs = erasure_locs;
+    a.stride = erasure_stride;
+    a.counts = erasure_counts;
+    return launch_rx_erasures(a, static_cast<hipStream_t>(stream));
+}
+
+int nfec_decode_received(nfec_codec* codec, const nfec_block_batch* batch, const uint32_t* received,
+                         uint32_t mask_stride, int32_t* status, void* stream)
+{
+    if (!codec || !batch) return fail(NFEC_EINVAL, "null codec or batch");
+    int rc = check_mask(codec, received, mask_stride);
+    if (rc) return rc;
+    if ((rc = check_batch(codec, batch)) || batch->nblocks == 0) return rc;
+    if (!(codec = stripe_for(codec, batch->blocks))) return fail(NFEC_EINVAL, "batch is not on a device of the codec");
+    DeviceGuard g(codec->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // the lists are decode workspace: held under the codec's mutex through the decode's own
+    // launches, and reused by the next call in stream order, as the plan's buffers are
+    std::lock_guard<std::mutex> lk(codec->mu);
+    const uint32_t lstride = std::max(codec->m, 1u);
+    if ((rc = codec->w_rxlocs.reserve((size_t)batch->nblocks * lstride))) return rc;
+    if ((rc = codec->w_rxcounts.reserve(batch->nblocks))) return rc;
+    RxErasureArgs a;
+    a.received = received;
+    a.mask_stride = mask_stride;
+    a.num_data = batch->num_data;
+    a.k = codec->k;
+    a.m = codec->m;
+    a.nblocks = batch->nblocks;
+    a.locs = codec->w_rxlocs.p;
+    a.stride = lstride;
+    a.counts = codec->w_rxcounts.p;
+    if ((rc = launch_rx_erasures(a, s))) return rc;
+    return decode_device(codec, batch, codec->w_rxlocs.p, lstride, codec->w_rxcounts.p, status, s, true);
 }
 
 // ---- per-call NORM semantics (synchronous, host vectors) ----

@@ -742,4 +742,38 @@ struct ErasureListArgs {
 };
 int launch_erasure_list(const ErasureListArgs& a, hipStream_t s);
 
+// Receiver assembly on the device (kernels_rx.hip; nfec.h "receiver assembly on the device").
+// Place: one wave per segment; lane 0 claims the slot's mask bit, the wave then copies the
+// payload from any byte alignment into the 8-byte aligned slot and zero-pads it to vec.
+struct RxPlaceArgs {
+    uint8_t* base = nullptr;             // the batch
+    uint64_t block_stride = 0;
+    uint32_t seg_stride = 0;
+    uint32_t nblocks = 0;
+    const uint16_t* num_data = nullptr;  // per block, or null = k
+    uint32_t k = 0, m = 0, vec = 0;
+    const uint8_t* payloads = nullptr;
+    const uint64_t* offsets = nullptr;
+    const uint32_t* block_index = nullptr;
+    const uint16_t* symbol_id = nullptr;
+    const uint16_t* length = nullptr;
+    uint32_t count = 0;
+    uint32_t* received = nullptr;        // [nblocks][mask_stride]
+    uint32_t mask_stride = 0;
+    uint32_t* stats = nullptr;           // [3] placed, duplicate, rejected (or null)
+};
+int launch_rx_place(const RxPlaceArgs& a, hipStream_t s);
+// Erasure lists from reception masks: one wave per block, lanes over mask words.
+struct RxErasureArgs {
+    const uint32_t* received = nullptr;
+    uint32_t mask_stride = 0;
+    const uint16_t* num_data = nullptr;  // per block, or null = k
+    uint32_t k = 0, m = 0;
+    uint32_t nblocks = 0;
+    uint16_t* locs = nullptr;
+    uint32_t stride = 0;
+    uint16_t* counts = nullptr;
+};
+int launch_rx_erasures(const RxErasureArgs& a, hipStream_t s);
+
 }  // namespace nfec

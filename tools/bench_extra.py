@@ -9,6 +9,10 @@ rs8   RS8 with --k/--m/--erasures (other shapes than the headline)
 rs8sweep  RS8 encode + decode over NORM-plausible shapes, one line per shape, with the time per
       source byte relative to (64, 32): (64,32), (16,4), (32,16), (64,16) shortened (numData
       drawn per block from [32, 64]), (128,32), (200,55), (64,8), (8,2) -- the generic-shape cliff
+rx    receiver assembly on the device, RS8 k=64 m=32 vec=1400, 65,536 blocks: 80 of each block's 96
+      segments arrive (16 source lost), in an order shuffled over the whole batch, payloads at a
+      1,413-byte pitch (every alignment occurs).  nfec_rx_place next to nfec_util_stream_copy of the
+      same byte count, nfec_decode_received next to nfec_decode on lists built beforehand
 
 Inputs are synthetic (splitmix64 segments generated on the GPU); GiB/s counts source bytes
 (k * vec per block) per pass, like the headline metric.
@@ -49,6 +53,8 @@ def main():
 
     if a.workload == "rs8sweep":
         return rs8_sweep(a)
+    if a.workload == "rx":
+        return rx_bench(a)
 
     shapes = {  # kind, k, m, blocks, erasures (0: encode only)
         "c4": (na.NFEC_RS16, 4096, 256, 4096, 0),
@@ -306,6 +312,121 @@ def rs8_sweep(a):
         }), flush=True)
         del blocks, keep, status, locs, counts
         torch.cuda.empty_cache()
+
+
+def rx_bench(a):
+    """place + decode_received against the streaming copy and the plain decode, one JSON line"""
+    import numpy as np
+    import torch
+    import norm_amd as na
+
+    torch.cuda.set_device(0)
+    stream = torch.cuda.current_stream()
+    k, m, vec, lost, pitch = a.k or 64, a.m or 32, a.vec, 16 if a.erasures < 0 else a.erasures, 1413
+    nb = a.blocks or 65536
+    n = k + m
+    enc, dec = na.NormEncoderRS8(), na.NormDecoderRS8()
+    assert enc.Init(k, m, vec) and dec.Init(k, m, vec)
+    stride = (vec + 7) & ~7
+    clean = torch.zeros((nb, n, stride), dtype=torch.uint8, device="cuda")
+    na.fill_blocks(clean, k, vec, 0x4E4F524D)
+    enc.encode_blocks(clean, stream=stream)
+    # the loss plan: `lost` source segments per block; every other segment arrives, in an order
+    # shuffled over the whole batch
+    locs, counts = na.make_erasures(nb, k, lost, 0x4E4F524D, m)
+    have = torch.ones((nb, n), dtype=torch.bool, device="cuda")
+    if lost:
+        have.scatter_(1, locs[:, :lost].long(), False)
+    ids = have.flatten().nonzero().flatten()
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(0x4E4F524D)
+    ids = ids[torch.randperm(ids.numel(), device="cuda", generator=gen)]
+    count = ids.numel()
+    assert count == nb * (n - lost)
+    block_index = (ids // n).to(torch.int32)
+    symbol_id = (ids % n).to(torch.int16)
+    length = torch.full((count,), vec, dtype=torch.int16, device="cuda")
+    offsets = torch.arange(count, dtype=torch.int64, device="cuda") * pitch
+    payloads = torch.empty(count * pitch + 16, dtype=torch.uint8, device="cuda")
+    payloads.fill_(0xA5)
+    rows = payloads[:count * pitch].view(count, pitch)
+    flat = clean.view(nb * n, stride)
+    for i0 in range(0, count, 1 << 18):
+        sl = slice(i0, min(count, i0 + (1 << 18)))
+        rows[sl, :vec] = flat[ids[sl], :vec]
+    batch = torch.empty_like(clean)
+    batch.fill_(0x5A)
+    mask = na.received_mask(nb, k, m)
+    stats = torch.zeros(3, dtype=torch.int32, device="cuda")
+    status = torch.empty(nb, dtype=torch.int32, device="cuda")
+    moved = count * vec
+    nbytes = moved & ~15
+    csrc = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    csrc.fill_(0x3C)
+    cdst = torch.empty_like(csrc)
+
+    def timed(fn, before=None):
+        """per-step times (ms) of fn alone: `before` runs untimed ahead of each step"""
+        out = []
+        for i in range(a.warmup + a.steps):
+            if before:
+                before()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            fn()
+            e1.record(stream)
+            e1.synchronize()
+            if i >= a.warmup:
+                out.append(e0.elapsed_time(e1))
+        return out
+
+    def place(st):
+        dec.place_segments(batch, mask, payloads, offsets, block_index, symbol_id, length, stats=st, stream=stream)
+
+    def med(v):
+        return float(np.median(v))
+
+    place_ms = timed(lambda: place(None), before=lambda: mask.zero_())
+    place_stats_ms = timed(lambda: place(stats), before=lambda: (mask.zero_(), stats.zero_()))
+    got_stats = stats.cpu().tolist()
+    copy_ms = timed(lambda: na.stream_copy(cdst, csrc, stream=stream))
+    # a second call finds every slot taken: the claim alone, no payload moved
+    dup_ms = timed(lambda: place(None))
+    elocs, ecounts = dec.erasures_from_received(mask, stream=stream)
+    lists_ms = timed(lambda: dec.erasures_from_received(mask, stream=stream))
+    lists_ok = bool(torch.equal(elocs, locs)) and bool(torch.equal(ecounts, counts))
+    placed = batch.clone()
+    dec_ms = timed(lambda: dec.decode_blocks(batch, elocs, ecounts, status=status, stream=stream))
+    batch.copy_(placed)
+    decrx_ms = timed(lambda: dec.decode_received(batch, mask, status=status, stream=stream))
+    # one clean pass, checked: place into the junk-filled batch, repair from the mask, compare
+    batch.fill_(0x5A)
+    mask.zero_()
+    place(None)
+    dec.decode_received(batch, mask, status=status, stream=stream)
+    torch.cuda.synchronize()
+    ok = bool((status == lost).all()) and lists_ok and got_stats == [count, 0, 0]
+    for b0 in range(0, nb, 4096):
+        ok &= bool(torch.equal(batch[b0:b0 + 4096, :k, :vec], clean[b0:b0 + 4096, :k, :vec]))
+    pm, cm = med(place_ms), med(copy_ms)
+    print(json.dumps({
+        "workload": "rx", "codec": "RS8", "k": k, "m": m, "vec": vec, "blocks": nb, "lost_source_per_block": lost,
+        "segments": count, "payload_pitch": pitch, "payload_GB": round(moved / 1e9, 3),
+        "steps": a.steps, "warmup": a.warmup,
+        "place_ms": round(pm, 3), "place_ms_min": round(min(place_ms), 3),
+        "place_GBps": round(moved / (pm * 1e-3) / 1e9, 1),
+        "place_with_stats_ms": round(med(place_stats_ms), 3),
+        "place_all_duplicates_ms": round(med(dup_ms), 3),
+        "stream_copy_bytes": nbytes, "stream_copy_ms": round(cm, 3), "stream_copy_ms_min": round(min(copy_ms), 3),
+        "stream_copy_GBps": round(nbytes / (cm * 1e-3) / 1e9, 1),
+        "place_rate_vs_stream_copy": round((moved / pm) / (nbytes / cm), 3),
+        "rx_erasures_ms": round(med(lists_ms), 4),
+        "decode_ms": round(med(dec_ms), 3), "decode_received_ms": round(med(decrx_ms), 3),
+        "decode_received_vs_decode": round(med(decrx_ms) / med(dec_ms), 3),
+        "decode_paths": {nm: c for nm, c in dec.decode_paths().items() if c},
+        "rate_note": "GB/s = payload bytes placed (or bytes copied) per second, each byte read once and written once",
+        "verified": ok,
+    }), flush=True)
 
 
 if __name__ == "__main__":

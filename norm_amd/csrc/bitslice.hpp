@@ -287,6 +287,13 @@ int launch_mdp_asm_encode(uint32_t k, uint32_t m, const bs::EncArgs& a, hipStrea
 // gen_rs8_q4.hip: 4 role waves per workgroup sharing each column's transpose through LDS
 int launch_rs8_q4_encode(uint32_t k, uint32_t m, const bs::EncArgs& a, hipStream_t s);
 int launch_mdp_q4_encode(uint32_t k, uint32_t m, const bs::EncArgs& a, hipStream_t s);
+// rs8_enc_d2.hip: (64, 32) with 2 role waves of 16 rows at 3 waves per SIMD (LDS-DMA column ring);
+// NFEC_ENOTSUP for every other shape and for the layouts launch_rs8_q4_encode keeps
+int launch_rs8_d2_encode(uint32_t k, uint32_t m, const bs::EncArgs& a, hipStream_t s);
+#ifdef NFEC_DIAG
+// gen_rs8_d2.hip (diagnostic library): its timing probes, NFEC_ENOTSUP unless NFEC_D2_VARIANT selects one
+int launch_rs8_d2_probe(uint32_t k, uint32_t m, const bs::EncArgs& a, hipStream_t s);
+#endif
 int launch_rs8_bitsliced_reencode(uint32_t k, uint32_t m, const bs::DecArgs& a, hipStream_t s);
 int bitsliced_encode_generator(uint32_t k, uint32_t m, uint8_t* out);
 

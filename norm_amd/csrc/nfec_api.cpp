@@ -1119,10 +1119,19 @@ static int encode_device_impl(nfec_codec* c, const nfec_block_batch* b, hipStrea
         if (use_asm() && use_q4() && (!nt || tail_ok)) {
             path = NFEC_PATH_FIXED;
             e.vec = vec8;
-            const int rc = launch_rs8_q4_encode(c->k, c->m, e, s);
+            // (64, 32): the 2-role-wave kernel at 3 waves per SIMD (rs8_enc_d2.hip) for the layouts it
+            // takes, every other shape and layout the 4-role-wave kernels (NFEC_ENC_D2=0, diagnostic
+            // library: off; read per call, so one process can run both)
+            const bool use_d2 = diag_knob("NFEC_ENC_D2", 1) != 0;
+            int rc = NFEC_ENOTSUP;
+#ifdef NFEC_DIAG
+            if (use_d2) rc = launch_rs8_d2_probe(c->k, c->m, e, s);  // NFEC_D2_VARIANT: a timing probe
+#endif
+            if (rc == NFEC_ENOTSUP && use_d2) rc = launch_rs8_d2_encode(c->k, c->m, e, s);
+            if (rc == NFEC_ENOTSUP) rc = launch_rs8_q4_encode(c->k, c->m, e, s);
             e.vec = c->vec;
             if (rc != NFEC_ENOTSUP) {
-                if (rc != NFEC_OK) return fail(rc, "q4 encode launch failed");
+                if (rc != NFEC_OK) return fail(rc, "fixed-generator encode launch failed");
                 if (!nt) return NFEC_OK;
                 tail = true;
                 return launch_encode_tail(ta, c->vec, s);

@@ -774,9 +774,10 @@ def f3_form_nargs(fmt):
     return 1 + max([int(x) for x in re.findall(r"\{(\d)\}", fmt)], default=-1)
 
 
-def f3_defines():
+def f3_defines(forms=None):
+    """forms: another kernel's instruction shapes (gen_rs8_d2.py), default fdec3's"""
     out = []
-    for name, fmt in F3_FORMS:
+    for name, fmt in forms or F3_FORMS:
         n = f3_form_nargs(fmt)
         text = '"' + re.sub(r"\{(\d)\}", lambda mt: '" #' + "abcd"[int(mt.group(1))] + ' "', fmt) + '\\n"'
         text = text.replace(' ""', "").replace('"" ', "")
@@ -790,7 +791,7 @@ def f3_defines():
     return out
 
 
-def f3_compact(lines, width=200):
+def f3_compact(lines, width=200, forms=None):
     """-> (defines, body): the asm lines as macro calls and string literals, packed into source
     lines; a registered run of instructions that occurs more than once becomes a macro K<n>"""
     lines = list(lines)
@@ -801,15 +802,15 @@ def f3_compact(lines, width=200):
         if len(hits) < 2 or n < 8:
             continue
         name = f"K{len(defs)}"
-        defs.append(f"#define {name} \\\n    " + " \\\n    ".join(f3_compact_lines(blk, width)))
+        defs.append(f"#define {name} \\\n    " + " \\\n    ".join(f3_compact_lines(blk, width, forms)))
         for i in reversed(hits):
             lines[i:i + n] = [f"\0{name}"]
-    return defs, f3_compact_lines(lines, width)
+    return defs, f3_compact_lines(lines, width, forms)
 
 
-def f3_compact_lines(lines, width):
+def f3_compact_lines(lines, width, forms=None):
     pats = []
-    for name, fmt in F3_FORMS:
+    for name, fmt in forms or F3_FORMS:
         seen, rx = set(), ""
         for part in re.split(r"(\{\d\})", fmt):
             if re.fullmatch(r"\{\d\}", part):

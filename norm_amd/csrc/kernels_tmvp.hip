@@ -1,4 +1,4 @@
-// RS16 encode by the Toeplitz split of the generator (rs16_tmvp in nfec_api.cpp).
+// RS16 encode by the Toeplitz split of the generator (rs16_tmvp*_encode in dispatch_encode.cpp).
 //
 // The RS16 generator of NormEncoderRS16::Init (src/common/normEncoderRS16.cpp:399-461) is the
 // Lagrange basis of the points x_0 = 0, x_j = alpha^(j-1) evaluated at y_p = alpha^(k-1+p):
@@ -15,7 +15,7 @@
 // gen_gf16_t3.hip, under NFEC_OPT_RS16_SHARED_TABLES, one level only); the kernels here are the elementwise steps around
 // them: bit-sliced multiplies by wave-uniform constants.  Two Karatsuba levels (nine products)
 // use the tmvp2_* pair below.  Any chunk width; vec % 8 != 0 runs over the 8-byte pieces and the
-// tail kernel takes the rest (rs16_tmvp_encode, nfec_api.cpp).
+// tail kernel takes the rest (rs16_tmvp_encode, dispatch_encode.cpp).
 #include "nfec_internal.hpp"
 #include "gf16_bs.hpp"
 #include "bitslice.hpp"

@@ -4,6 +4,8 @@
 // :542-649; normEncoderRS16.cpp:399-461; normEncoderMDP.cpp:56-84): it owns the generator
 // (built once on the host, uploaded to HBM) and the per-value kernel tables.  Batched calls
 // only enqueue kernels on the caller's stream; no host<->device traffic on the hot path.
+// The codec object is in codec_state.hpp; which kernels a device batch reaches is decided in
+// dispatch_encode.cpp and dispatch_decode.cpp.
 #include <algorithm>
 #include <condition_variable>
 #include <cstdio>
@@ -19,305 +21,9 @@
 #include <vector>
 
 #include "bitslice.hpp"
-#include "nfec_internal.hpp"
-
-namespace nfec {
-const char* last_error_cstr();
-}
+#include "codec_state.hpp"
 
 using namespace nfec;
-
-namespace {
-
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = true;
-    explicit DeviceGuard(int dev)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard()
-    {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    int reserve(size_t count)
-    {
-        if (count <= n) return NFEC_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(NFEC_ENOMEM, "hipMalloc failed for workspace");
-        }
-        n = count;
-        return NFEC_OK;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
-
-constexpr uint32_t kRowPad = 32;       // coefficient rows padded (kernel row chunk multiple)
-// decode blocks per planning pass: bounds the workspace (stage-1 rows z, plan matrices).
-// Larger passes measured faster (fewer, fuller launches: 16k -> 64k blocks took
-// decode from 2.92 to 2.77 ms per 64k blocks), so a pass is as large as 8 GiB of workspace
-// allows (3 % of an MI355X's 288 GB).
-// budget_bytes caps it further (decode_device: half of the device memory free plus what the
-// codec already holds).  NFEC_SUBBATCH overrides (A/B runs, diagnostic library).
-static uint32_t sub_batch(uint64_t ws_bytes_per_block, uint64_t budget_bytes = 8ull << 30, uint32_t max_blocks = 65536)
-{
-    static const long env = diag_knob("NFEC_SUBBATCH", 0, 0, 1L << 20);
-    if (env > 0) return (uint32_t)std::max(256L, std::min(env, 1L << 20));
-    const uint64_t cap = std::min<uint64_t>(8ull << 30, budget_bytes) / std::max<uint64_t>(ws_bytes_per_block, 1);
-    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(max_blocks, cap));
-}
-
-uint32_t round_up(uint32_t v, uint32_t a) { return (v + a - 1) / a * a; }
-
-}  // namespace
-
-constexpr uint32_t kHostSlots = 3;
-struct HostSlot {
-    uint8_t* dev = nullptr;
-    uint8_t* pin = nullptr;     // pinned staging (pageable callers, segment lists)
-    uint8_t* pin_dev = nullptr; // the same staging as the device addresses it (zero-copy kernels)
-    uint16_t* dmeta = nullptr;  // num_data, erasure locs, counts
-    uint8_t* hmeta = nullptr;   // pinned mirror of dmeta (meta_up)
-    int32_t* dstat = nullptr;
-    int32_t* hstat = nullptr;   // pinned status readback
-    hipStream_t st = nullptr;
-    hipEvent_t done = nullptr, ev_up = nullptr, ev_cd = nullptr;
-    size_t dev_bytes = 0, pin_bytes = 0, meta_bytes = 0, dstat_bytes = 0, hstat_bytes = 0, hmeta_bytes = 0;
-};
-
-// host-batch pipeline resources cached per codec (run_host_batch / run_host_vectors)
-struct HostStage {
-    HostSlot slot[kHostSlots];
-    hipStream_t cst = nullptr;  // decode compute stream
-    void release()
-    {
-        for (auto& s : slot) {
-            if (s.st) (void)hipStreamSynchronize(s.st);
-            if (s.dev) (void)hipFree(s.dev);
-            if (s.pin) (void)hipHostFree(s.pin);
-            if (s.dmeta) (void)hipFree(s.dmeta);
-            if (s.hmeta) (void)hipHostFree(s.hmeta);
-            if (s.dstat) (void)hipFree(s.dstat);
-            if (s.hstat) (void)hipHostFree(s.hstat);
-            if (s.done) (void)hipEventDestroy(s.done);
-            if (s.ev_up) (void)hipEventDestroy(s.ev_up);
-            if (s.ev_cd) (void)hipEventDestroy(s.ev_cd);
-            if (s.st) (void)hipStreamDestroy(s.st);
-            s = HostSlot();
-        }
-        if (cst) {
-            (void)hipStreamSynchronize(cst);
-            (void)hipStreamDestroy(cst);
-            cst = nullptr;
-        }
-    }
-};
-
-// An asynchronous host-batch call (nfec_*_host_vectors_async): the arguments are copied at
-// submission, a codec-owned worker thread runs the call, the caller polls or waits.
-struct nfec_request {
-    std::mutex mu;
-    std::condition_variable cv;
-    bool done = false;
-    int rc = NFEC_OK;
-    std::string err;  // the worker thread's error message, handed to the waiting thread
-    std::function<int()> run;
-};
-
-// One worker thread per codec that has seen an async call: requests on a codec complete in
-// submission order (they share the codec's staging pipeline anyway); codecs run concurrently,
-// so a receiver with one decoder per remote sender (normNode.h:649) overlaps its senders.
-struct AsyncQueue {
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<nfec_request*> q;
-    std::thread th;
-    bool stop = false;
-    int device = 0;
-
-    void loop()
-    {
-        (void)hipSetDevice(device);
-        for (;;) {
-            nfec_request* r = nullptr;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return stop || !q.empty(); });
-                if (q.empty()) return;  // stop requested and drained
-                r = q.front();
-                q.pop_front();
-            }
-            const int rc = r->run();
-            std::lock_guard<std::mutex> lk(r->mu);
-            if (rc < 0) r->err = last_error_cstr();
-            r->rc = rc;
-            r->done = true;
-            r->cv.notify_all();
-        }
-    }
-    void submit(nfec_request* r)
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (!th.joinable()) th = std::thread([this] { loop(); });
-        q.push_back(r);
-        cv.notify_one();
-    }
-    // finishes every queued request, then stops the thread
-    void shutdown()
-    {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            stop = true;
-            cv.notify_all();
-        }
-        if (th.joinable()) th.join();
-    }
-};
-
-struct nfec_codec {
-    int kind = 0;
-    int device = 0;
-    uint32_t opts = 0;  // NFEC_OPT_* (nfec_codec_create_ex)
-    uint32_t k = 0, m = 0, vec = 0, sym = 1;
-    // a codec over several devices (nfec_codec_create_ex): one full single-device codec per
-    // listed device.  Host batches are striped over them in contiguous block ranges; device
-    // batches run on the stripe of the batch's device; per-call work on stripe 0.  The outer
-    // codec keeps the shape and the generator but no device state.
-    std::vector<std::unique_ptr<nfec_codec>> stripes;
-    uint32_t cs = 0;  // padded parity-row count
-    std::vector<uint32_t> gen;  // m x k parity rows (RS) / LFSR map for a full block (MDP)
-    std::vector<uint8_t> mdp_g; // MDP generator polynomial g[0..m] (the host per-segment step)
-
-    // device-resident state
-    DevBuf<uint8_t> d_coef;      // encode coefficients, column-major [k][cs] elements
-    DevBuf<uint8_t> d_gen;       // m x k row-major elements (decode plan gathers)
-    DevBuf<uint32_t> d_vtab;     // 256 x 8 dwords (GF(2^8) kernels)
-    DevBuf<uint8_t> d_exp;       // field exp table (2q elements)
-    DevBuf<uint16_t> d_log;      // field log table (q+1)
-    DevBuf<uint8_t> d_mdp_step;  // MDP single LFSR step matrix, column-major [m+1][cs]
-    DevBuf<uint16_t> d_lwp, d_lw;  // RS8 closed-form plan constants: log W'(x_j), log W(y_p)
-    std::vector<uint16_t> h_lwp, h_lw;  // the same on the host (nfec_decode_vectors_host)
-    // RS8 / MDP products with runtime coefficients (gen_rs8_rt.hip): the generator as snippet
-    // offsets [k][m] (RS8), or one [k][m] table per block length nd = 1..k (MDP, shortened)
-    DevBuf<uint16_t> d_rt;
-    uint64_t rt_block_bytes = 0;   // MDP: bytes per numData table
-    DevBuf<uint16_t> d_sel16;      // RS16 bit-sliced encode table offsets [k][m][64] (may be absent)
-    DevBuf<uint16_t> d_t3off;      // RS16 shared-table encode LDS offsets [k+1][m_pad][48]
-    // RS16 products by the tower-field kernel (gen_gf16_tw.hip) instead of the shared-table one:
-    // snippet offsets [k][sweep][m][2] (gf16_tw_table_elems); the Toeplitz split's products likewise
-    bool tw = false;
-    // NFEC_OPT_HOST_ONLY: no device, no device tables; only the host per-call paths run
-    bool host_only = false;
-    DevBuf<uint16_t> d_twoff, d_tmvp_tw;
-    // RS16 encode by the Toeplitz split (kernels_tmvp.hip): offsets of the three products, each
-    // [k/2+1][m_pad(m/2)][48], then the constants' row masks (c_j [k][16], W [m][16], G0 [m][16])
-    bool tmvp = false;
-    int tmvp_levels = 0;           // Karatsuba levels of the split: 1 (3 products) or 2 (9, tower kernel)
-    DevBuf<uint16_t> d_tmvp_off, d_tmvp_mat;
-    std::mutex tmvp_mu;            // one Toeplitz encode at a time per codec: they share w_tmvp
-    DevBuf<uint8_t> w_tmvp;        // prescaled pair sums + P1 rows of a sub-batch
-    hipEvent_t tmvp_done = nullptr;  // the last Toeplitz encode's end, on its stream
-    // two-level encode pipeline (rs16_tmvp2_encode): a second stream of the codec's own and the
-    // events that fork it from the caller's stream, stagger the sub-batches' prescales and join
-    hipStream_t tmvp_s2 = nullptr;
-    hipEvent_t tmvp_ev[4] = {};      // fork, join, prescale done (two, alternating)
-    // device-batch encodes per path that took them (NFEC_PATH_*, nfec_codec_encode_paths)
-    std::atomic<uint64_t> enc_paths[NFEC_PATH_COUNT] = {};
-    std::atomic<uint64_t> dec_paths[NFEC_DPATH_COUNT] = {};  // ... and decodes (NFEC_DPATH_*)
-    // device batches whose last vec % 8 bytes ran on the tail kernels (encodes, decodes)
-    std::atomic<uint64_t> tail_batches[2] = {};
-
-    // decode workspace (guarded by mu)
-    std::mutex mu;
-    DevBuf<int32_t> w_status, w_rows, w_rows1;
-    DevBuf<uint32_t> w_rmax;
-    DevBuf<uint16_t> w_islots, w_oslots, w_cols;
-    DevBuf<uint8_t> w_coef1, w_coef2, w_z, w_work, w_pmap;
-    DevBuf<uint32_t> w_emask, w_psel, w_gate;
-    DevBuf<uint16_t> w_tw2;        // RS16 decode stage 2 on the tower kernel: per-block tables
-    DevBuf<uint32_t> w_rowoff;     // ... and output row offsets (TwDecTablesArgs)
-    uint32_t gate_gen = 0;         // per-pass generation written into w_gate (RsPlan2Args)
-    DevBuf<uint16_t> w_rxlocs, w_rxcounts;  // nfec_decode_received: the lists built from the mask ([b][m], [b])
-    // per-call staging (nfec_encode_segment / nfec_decode_vectors, guarded by mu): one device
-    // buffer and one pinned mirror of the same layout, and a stream of the codec's own, so a
-    // call is one gather, one H2D, the kernels, one D2H and one scatter
-    DevBuf<uint8_t> s_block;
-    uint8_t* s_pin = nullptr;
-    size_t s_pin_bytes = 0;
-    hipStream_t s_stream = nullptr;
-    // host-batch pipelines (slots, pinned staging, streams): one host-batch call at a time per
-    // codec.  Separate from mu, which the decode kernels' workspace takes inside such a call.
-    std::mutex stage_mu;
-    HostStage stage;
-    AsyncQueue async;
-
-    ~nfec_codec()
-    {
-        async.shutdown();  // outstanding async requests complete before the codec goes away
-        // a host-only codec (device -1) holds no device state and never starts the HIP runtime
-        // (hipSetDevice(-1) would also leave an error in this thread's last-error slot)
-        if (host_only || device < 0) return;
-        DeviceGuard g(device);
-        stage.release();
-        for (auto* b : {&d_coef, &d_gen, &d_exp, &w_coef1, &w_coef2, &w_z, &w_work, &s_block, &d_mdp_step, &w_tmvp})
-            b->release();
-        if (s_stream) {
-            (void)hipStreamSynchronize(s_stream);
-            (void)hipStreamDestroy(s_stream);
-        }
-        if (s_pin) (void)hipHostFree(s_pin);
-        d_tmvp_off.release();
-        d_tmvp_mat.release();
-        if (tmvp_done) (void)hipEventDestroy(tmvp_done);
-        if (tmvp_s2) {
-            (void)hipStreamSynchronize(tmvp_s2);
-            (void)hipStreamDestroy(tmvp_s2);
-        }
-        for (hipEvent_t ev : tmvp_ev)
-            if (ev) (void)hipEventDestroy(ev);
-        d_vtab.release();
-        d_log.release();
-        d_lwp.release();
-        d_lw.release();
-        d_rt.release();
-        d_sel16.release();
-        d_t3off.release();
-        d_twoff.release();
-        d_tmvp_tw.release();
-        w_pmap.release();
-        w_emask.release();
-        w_psel.release();
-        w_gate.release();
-        w_status.release();
-        w_rows.release();
-        w_rows1.release();
-        w_rmax.release();
-        w_islots.release();
-        w_oslots.release();
-        w_cols.release();
-        w_tw2.release();
-        w_rowoff.release();
-        w_rxlocs.release();
-        w_rxcounts.release();
-    }
-};
 
 namespace {
 
@@ -333,6 +39,10 @@ int host_only_fail()
 {
     return fail(NFEC_EDEVICE, "host-only codec (NFEC_OPT_HOST_ONLY): no GPU path");
 }
+
+}  // namespace
+
+namespace nfec {
 
 int check_batch(const nfec_codec* c, const nfec_block_batch* b)
 {
@@ -364,35 +74,9 @@ bool use_gf16_tw(const nfec_codec* c)
     return diag_knob("NFEC_RS16_TW", (c->opts & NFEC_OPT_RS16_SHARED_TABLES) ? 0 : 1) != 0;
 }
 
-// one RS16 product (encode, decode stage 1) on the codec's product kernel
-static int launch_rs16_product(const nfec_codec* c, const Gf16T3Args& t, hipStream_t s)
-{
-    return c->tw ? launch_gf16_tw_encode(t, s) : launch_gf16_t3_encode(t, s);
-}
+}  // namespace nfec
 
-// one RS16 product on the tower kernel over a whole vector of t.vec_bytes (even) bytes: its
-// 8-byte pieces on the tower kernel, the 2-6 byte tail past them on the tail kernel
-// (kernels_gf16tail.hip), so any NORM vector size (segmentSize + 8) stays off the exp-table kernel
-static bool rs16_tw_full_covers(const Gf16T3Args& t)
-{
-    const uint32_t even = t.vec_bytes & ~1u, body = even & ~7u;
-    if (even == 0) return false;
-    Gf16T3Args b = t;
-    b.vec_bytes = body;
-    return (body == 0 || gf16_tw_covers(b)) && gf16_tw_tail_covers(t, even - body);
-}
-
-static int launch_rs16_tw_full(const Gf16T3Args& t, hipStream_t s)
-{
-    const uint32_t even = t.vec_bytes & ~1u, body = even & ~7u;
-    if (body) {
-        Gf16T3Args b = t;
-        b.vec_bytes = body;
-        const int rc = launch_gf16_tw_encode(b, s);
-        if (rc) return rc;
-    }
-    return launch_gf16_tw_tail(t, body, even - body, s);
-}
+namespace {
 
 // ---- codec construction ----
 // log W'(x_j) over the k source points and log W(y_p) at the parity points: the constants of
@@ -661,6 +345,10 @@ int build_codec(nfec_codec* c)
     return NFEC_OK;
 }
 
+}  // namespace
+
+namespace nfec {
+
 // NFEC_FORCE_GENERIC=1 disables the generated bit-sliced kernels (A/B runs, diagnostic library)
 bool force_generic()
 {
@@ -689,7 +377,7 @@ bool has_bitsliced(uint32_t k, uint32_t m)
 // tuning knobs of the bit-sliced kernels (A/B runs): bit 0 XCD-contiguous workgroup
 // mapping (default on: neighbouring item groups share the 128-byte lines at their boundaries,
 // so one XCD's L2 fetches them once; encode 2.38 -> 2.35 ms), bit 1 nontemporal parity stores
-static uint32_t bs_flags()
+uint32_t bs_flags()
 {
     static const uint32_t f = (uint32_t)diag_knob("NFEC_BS_FLAGS", 1, 0, 3);
     return f;
@@ -697,1469 +385,20 @@ static uint32_t bs_flags()
 
 // NFEC_Q4=0 (diagnostic library) replaces the 4-role-wave encode kernels (gen_rs8_q4.hip) by
 // the round-1 2-role assembly kernels, which only the diagnostic library builds
-static bool use_q4()
+bool use_q4()
 {
     static const bool v = diag_knob("NFEC_Q4", 1) != 0;
     return v;
 }
 
 // NFEC_ASM=0 (diagnostic library): compiler-allocated bit-sliced kernels only
-static bool use_asm()
+bool use_asm()
 {
     static const bool v = diag_knob("NFEC_ASM", 1) != 0;
     return v;
 }
 
-// ---- encode on a device batch ----
-// RS16 encode by the Toeplitz split (kernels_tmvp.hip): per sub-batch the prescale of the chunk
-// pairs, the three shared-table products in one launch, and the postscale into the parity.
-// The sub-batch scratch is the codec's, so calls are ordered: each waits (on its stream) for
-// the previous one's end.
-// Two Karatsuba levels (tower kernel only): the level-2 prescale writes the pair sums and the
-// scaled sums into the block's scratch, launches of the nine (m/4)-row products run into the
-// scratch -- each reads, through a column map, the alpha input of its last alpha level (its later
-// beta level selects halves) or, with no alpha in its path, the source columns themselves (c
-// folded into its coefficients) -- and the level-2 postscale combines them into the m parity rows
-// (kernels_tmvp.hip; gf_host.cpp, rs16_tmvp_plan_levels, whose product paths index them).
-static int rs16_tmvp2_encode(nfec_codec* c, const nfec_block_batch* b, hipStream_t s)
-{
-    const int L = c->tmvp_levels;
-    const uint32_t k = c->k, m = c->m, r = m >> L, cols = k >> L, vec = c->vec & ~7u;
-    uint32_t nprod = 1;
-    for (int i = 0; i < L; ++i) nprod *= 3;
-    const uint32_t prow0 = k / 2 + 3 * (k / 4);                 // first product row in the scratch
-    const uint64_t per_block = (uint64_t)(prow0 + nprod * r) * vec;
-    std::lock_guard<std::mutex> lk(c->tmvp_mu);
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
-        (void)hipGetLastError();
-        free_b = 0;
-    }
-    const uint64_t budget = std::min<uint64_t>(16ull << 30, ((uint64_t)free_b + c->w_tmvp.n) / 2);
-    // pipeline: the batch runs as sub-batches whose products launch has about 3,072 workgroups
-    // (12 per CU), alternating between the caller's stream and the codec's second one, each
-    // stream with its own half of the scratch, each prescale after the previous sub-batch's.  A
-    // launch's tail (its last workgroups leave CUs idle) then fills with the other stream's
-    // kernels, and the HBM-bound scale kernels run beside the issue-bound products.  Measured
-    // (profiles/r06/tmvp_pipe/, one box): RS16(400,100) encode 19.6-19.8 -> 19.1 ms at 16
-    // sub-batches (8: 19.2, 32: 19.3, 2-4: no gain), C4 96.3 -> 91.9 ms at 16.
-    // NFEC_TMVP_PIPE (knob library): 0 this rule, 1 off, N >= 2 at least N sub-batches
-    static const long pipe = diag_knob("NFEC_TMVP_PIPE", 0, 0, 64);
-    uint64_t want = 1;
-    if (pipe == 0) {
-        const uint64_t wg_x4096 = (uint64_t)nprod * (gf16_tw_passes(r, gf16_tw_rows(r)) / 4u) * vec;  // x 4096 per block
-        const uint64_t target = std::max<uint64_t>(1, 3072ull * 4096ull / std::max<uint64_t>(wg_x4096, 1));
-        want = (b->nblocks + target - 1) / target;
-    } else if (pipe >= 2) {
-        want = (uint64_t)pipe;
-    }
-    const bool piped = want >= 2 && b->nblocks >= 2;
-    const uint32_t nbuf = piped ? 2u : 1u;
-    const uint64_t cap = std::max<uint64_t>(1, budget / nbuf / per_block);
-    const uint64_t nsub = std::max<uint64_t>((b->nblocks + cap - 1) / cap, piped ? want : 1u);
-    const uint32_t sb = (uint32_t)std::max<uint64_t>(1, (b->nblocks + nsub - 1) / std::max<uint64_t>(nsub, 1));
-    if (c->w_tmvp.reserve((size_t)nbuf * sb * per_block) != NFEC_OK) {
-        (void)hipGetLastError();
-        return NFEC_ENOTSUP;  // no room for the scratch: the one-product encode takes the batch
-    }
-    if (piped && !c->tmvp_s2) {
-        if (hipStreamCreateWithFlags(&c->tmvp_s2, hipStreamNonBlocking) != hipSuccess)
-            return hip_fail(hipGetLastError(), "tmvp pipeline stream");
-        for (hipEvent_t& ev : c->tmvp_ev)
-            NFEC_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    }
-    NFEC_HIP(hipStreamWaitEvent(s, c->tmvp_done, 0));
-    bool queued = false, forked = false;
-    auto leave = [&](int code) {
-        // the second stream's work joins the caller's before tmvp_done, so the next encode (any
-        // stream) waits for both halves of the scratch
-        if (forked && (hipEventRecord(c->tmvp_ev[1], c->tmvp_s2) != hipSuccess ||
-                       hipStreamWaitEvent(s, c->tmvp_ev[1], 0) != hipSuccess) && code == NFEC_OK)
-            code = hip_fail(hipGetLastError(), "tmvp pipeline join");
-        if (queued && hipEventRecord(c->tmvp_done, s) != hipSuccess && code == NFEC_OK)
-            code = hip_fail(hipGetLastError(), "tmvp event");
-        return code;
-    };
-    const size_t one_tw = gf16_tw_table_elems(cols, r);
-    int rc;
-    uint32_t sub = 0;
-    for (uint32_t b0 = 0; b0 < b->nblocks; b0 += sb, ++sub) {
-        const uint32_t nb = std::min(sb, b->nblocks - b0);
-        uint8_t* blocks = static_cast<uint8_t*>(b->blocks) + (uint64_t)b0 * b->block_stride;
-        hipStream_t st = s;
-        if (piped && (sub & 1u)) {
-            if (!forked) {  // the second stream starts after everything before on the caller's
-                if (hipEventRecord(c->tmvp_ev[0], s) != hipSuccess ||
-                    hipStreamWaitEvent(c->tmvp_s2, c->tmvp_ev[0], 0) != hipSuccess)
-                    return leave(hip_fail(hipGetLastError(), "tmvp pipeline fork"));
-                forked = true;
-            }
-            st = c->tmvp_s2;
-        }
-        // the previous sub-batch's prescale first (the other stream); an error leaves through
-        // leave(), so tmvp_done still covers what both streams already hold
-        if (piped && sub > 0 && forked && hipStreamWaitEvent(st, c->tmvp_ev[2 + ((sub - 1) & 1u)], 0) != hipSuccess)
-            return leave(hip_fail(hipGetLastError(), "tmvp pipeline wait"));
-        Rs16TmvpArgs a;
-        a.base = blocks;
-        a.block_stride = b->block_stride;
-        a.seg_stride = b->seg_stride;
-        a.nblocks = nb;
-        a.vec = vec;
-        a.k = k;
-        a.cw = m / 2;
-        a.hw = r;
-        a.sc = c->w_tmvp.p + (piped ? (uint64_t)(sub & 1u) * sb * per_block : 0u);
-        a.sc_block_stride = per_block;
-        a.cmat = c->d_tmvp_mat.p;
-        a.wmat = c->d_tmvp_mat.p + (size_t)k * 16;
-        a.gmat = c->d_tmvp_mat.p + (size_t)(k + m) * 16;
-        a.num_data = b->num_data ? b->num_data + b0 : nullptr;
-        std::vector<Gf16T3Args> e(nprod);
-        for (uint32_t pi = 0; pi < nprod; ++pi) {
-            int dg[3] = {0, 0, 0};
-            for (int l = L, t = (int)pi; l >= 1; --l, t /= 3) dg[l - 1] = t % 3;
-            int last_alpha = 0;
-            for (int l = 1; l <= L; ++l)
-                if (dg[l - 1] == 0) last_alpha = l;
-            uint32_t off = 0;  // the beta levels after the last alpha select second halves
-            for (int l = last_alpha + 1; l <= L; ++l)
-                if (dg[l - 1] == 1) off += m >> l;
-            Gf16T3Args& g = e[pi];
-            g.nblocks = nb;
-            g.k = cols;
-            g.m = r;
-            g.vec_bytes = vec;
-            g.tw = c->d_tmvp_tw.p + pi * one_tw;
-            g.out_base = a.sc;
-            g.out_block_stride = per_block;
-            g.out_seg_stride = vec;
-            g.out_slot0 = prow0 + pi * r;
-            if (last_alpha == 0) {  // the source columns q m + i + off, chunks of m
-                g.base = blocks;
-                g.block_stride = b->block_stride;
-                g.seg_stride = b->seg_stride;
-                g.col_div = r;
-                g.col_chunk = m;
-                g.col_base = off;
-                g.in_slots = k + m;
-                // shortened blocks: a source slot at or past the block's numData reads zeros
-                g.num_data = a.num_data;
-                g.nd_limit = k;
-                continue;
-            }
-            // the alpha input of level last_alpha (block of prefix P' = the digits before it),
-            // column q (m >> last_alpha) + i + off
-            uint32_t pre = 0;
-            for (int l = 1; l < last_alpha; ++l) pre = pre * 3 + (uint32_t)dg[l - 1];
-            const uint32_t blk = (last_alpha == 1 ? 0u : k / 2) + pre * (k >> last_alpha);  // level 1: pair sums; 2: s_X
-            g.base = a.sc;
-            g.block_stride = per_block;
-            g.seg_stride = vec;
-            g.in_slots = prow0;
-            if (last_alpha == L) {
-                g.col_base = blk;  // plain columns
-            } else {
-                g.col_div = r;
-                g.col_chunk = m >> last_alpha;
-                g.col_base = blk + off;
-            }
-        }
-        // a shape the kernels do not cover shows on the first sub-batch, before any parity byte
-        // is written: NFEC_ENOTSUP then hands the batch to the one-product encode
-        if ((rc = launch_tmvp2_prescale(a, st)))
-            return leave(rc == NFEC_ENOTSUP && b0 == 0 ? rc : fail(rc, "tmvp multi-level prescale"));
-        queued = true;
-        if (piped && hipEventRecord(c->tmvp_ev[2 + (sub & 1u)], st) != hipSuccess)
-            return leave(hip_fail(hipGetLastError(), "tmvp pipeline event"));
-        for (uint32_t e0 = 0; e0 < nprod; e0 += kTwMultiMax)
-            if ((rc = launch_gf16_tw_multi(e.data() + e0, std::min<uint32_t>(kTwMultiMax, nprod - e0), st)))
-                return leave(rc == NFEC_ENOTSUP && b0 == 0 && e0 == 0 ? rc : fail(rc, "tmvp multi-level products"));
-        if ((rc = launch_tmvp2_postscale(a, st))) return leave(fail(rc, "tmvp multi-level postscale"));
-    }
-    return leave(NFEC_OK);
-}
-
-static int rs16_tmvp1_encode(nfec_codec* c, const nfec_block_batch* b, hipStream_t s);
-
-// the split over the vector's 8-byte pieces, then (vec % 8 != 0) its last 2-6 bytes on the tail
-// kernel with the whole generator: the product is the same at every byte position, so the split
-// and the tail write disjoint bytes of the same parity
-int rs16_tmvp_encode(nfec_codec* c, const nfec_block_batch* b, hipStream_t s)
-{
-    const int rc = c->tmvp_levels == 2 ? rs16_tmvp2_encode(c, b, s) : rs16_tmvp1_encode(c, b, s);
-    const uint32_t even = c->vec & ~1u, body = even & ~7u;
-    if (rc || even == body) return rc;
-    Gf16T3Args t;
-    t.base = static_cast<const uint8_t*>(b->blocks);
-    t.block_stride = b->block_stride;
-    t.seg_stride = b->seg_stride;
-    t.nblocks = b->nblocks;
-    t.k = c->k;
-    t.m = c->m;
-    t.vec_bytes = even;
-    t.tw = c->d_twoff.p;
-    t.num_data = b->num_data;
-    const int tr = launch_gf16_tw_tail(t, body, even - body, s);
-    return tr ? fail(tr, "tmvp vector tail") : NFEC_OK;
-}
-
-static int rs16_tmvp1_encode(nfec_codec* c, const nfec_block_batch* b, hipStream_t s)
-{
-    const uint32_t k = c->k, m = c->m, cw = m / 2, half = k / 2, vec = c->vec & ~7u;
-    // sub-batches of at most 16 GiB of scratch (C4's 4,096 blocks: one, 12.5 GB) and at most
-    // half of the device memory free now (plus the scratch this codec already holds), of equal
-    // size so no launch runs a small tail batch
-    const uint64_t per_block = (uint64_t)(half + cw) * vec;
-    std::lock_guard<std::mutex> lk(c->tmvp_mu);
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
-        (void)hipGetLastError();
-        free_b = 0;
-    }
-    const uint64_t budget = std::min<uint64_t>(16ull << 30, ((uint64_t)free_b + c->w_tmvp.n) / 2);
-    const uint64_t cap = std::max<uint64_t>(1, budget / per_block);
-    const uint64_t nsub = (b->nblocks + cap - 1) / cap;
-    const uint32_t sb = (uint32_t)std::max<uint64_t>(1, (b->nblocks + nsub - 1) / std::max<uint64_t>(nsub, 1));
-    // no room for the scratch: the one-product shared-table encode (no scratch) takes the batch
-    if (c->w_tmvp.reserve((size_t)sb * per_block) != NFEC_OK) {
-        (void)hipGetLastError();
-        return NFEC_ENOTSUP;
-    }
-    NFEC_HIP(hipStreamWaitEvent(s, c->tmvp_done, 0));
-    // once a kernel that writes the scratch is queued, every exit records tmvp_done after it, so
-    // the next Toeplitz encode (any stream) waits for it even when this one hands over
-    bool queued = false;
-    auto leave = [&](int code) {
-        if (queued && hipEventRecord(c->tmvp_done, s) != hipSuccess && code == NFEC_OK)
-            code = hip_fail(hipGetLastError(), "tmvp event");
-        return code;
-    };
-    int rc;
-    const uint32_t mp = gf16_t3_rows_padded(cw);
-    const size_t one = (size_t)(half + 1) * mp * 48;
-    const size_t one_tw = gf16_tw_table_elems(half, cw);
-    uint32_t shift = 0;
-    while ((1u << shift) < cw) ++shift;
-    for (uint32_t b0 = 0; b0 < b->nblocks; b0 += sb) {
-        const uint32_t nb = std::min(sb, b->nblocks - b0);
-        uint8_t* blocks = static_cast<uint8_t*>(b->blocks) + (uint64_t)b0 * b->block_stride;
-        Rs16TmvpArgs a;
-        a.base = blocks;
-        a.block_stride = b->block_stride;
-        a.seg_stride = b->seg_stride;
-        a.nblocks = nb;
-        a.vec = vec;
-        a.k = k;
-        a.cw = cw;
-        a.s = c->w_tmvp.p;
-        a.s_block_stride = (uint64_t)half * vec;
-        a.x = c->w_tmvp.p + (uint64_t)sb * half * vec;
-        a.x_block_stride = (uint64_t)cw * vec;
-        a.cmat = c->d_tmvp_mat.p;
-        a.wmat = c->d_tmvp_mat.p + (size_t)k * 16;
-        a.gmat = c->d_tmvp_mat.p + (size_t)(k + m) * 16;
-        a.num_data = b->num_data ? b->num_data + b0 : nullptr;
-        Gf16T3Args e[3];
-        for (int i = 0; i < 3; ++i) {
-            e[i].nblocks = nb;
-            e[i].k = half;
-            e[i].m = cw;
-            e[i].m_pad = mp;
-            e[i].vec_bytes = vec;
-            if (c->tw) e[i].tw = c->d_tmvp_tw.p + i * one_tw;
-            else e[i].offs = c->d_tmvp_off.p + i * one;
-            e[i].base = blocks;
-            e[i].block_stride = b->block_stride;
-            e[i].seg_stride = b->seg_stride;
-            e[i].out_base = blocks;
-            e[i].out_block_stride = b->block_stride;
-            e[i].out_seg_stride = b->seg_stride;
-        }
-        // P0 = A (pair sums) -> parity rows [k, k + cw)
-        e[0].base = a.s;
-        e[0].block_stride = a.s_block_stride;
-        e[0].seg_stride = vec;
-        e[0].out_slot0 = k;
-        // P1 over the second column of every pair -> x rows
-        e[1].col_shift = shift;
-        e[1].col_mask = cw - 1;
-        e[1].col_div = c->tw ? cw : 0;  // (any chunk width on the tower kernel)
-        e[1].col_chunk = 2 * cw;
-        e[1].col_base = cw;
-        e[1].in_slots = k + m;
-        e[1].out_base = a.x;
-        e[1].out_block_stride = a.x_block_stride;
-        e[1].out_seg_stride = vec;
-        e[1].out_slot0 = 0;
-        // P2 over the first column of every pair -> parity rows [k + cw, k + m)
-        e[2].col_shift = shift;
-        e[2].col_mask = cw - 1;
-        e[2].col_div = c->tw ? cw : 0;
-        e[2].col_chunk = 2 * cw;
-        e[2].col_base = 0;
-        e[2].in_slots = k + m;
-        e[2].out_slot0 = k + cw;
-        if (a.num_data) {
-            // shortened blocks (tower kernel only): P1 and P2 mask the source slots at or past
-            // the block's numData; P0 (over the pair sums) and P2 write the parity rows after
-            // it, slot numData + r
-            for (int i = 0; i < 3; ++i) {
-                e[i].num_data = a.num_data;
-                e[i].nd_limit = k;
-            }
-            e[0].nd_outputs_only = 1;
-            e[0].out_slot0 = 0;
-            e[0].out_after_data = 1;
-            e[2].out_slot0 = cw;
-            e[2].out_after_data = 1;
-        }
-        // a shape the kernels do not cover shows on the first sub-batch, before any parity byte
-        // is written: NFEC_ENOTSUP then hands the batch to the one-product encode
-        if ((rc = launch_tmvp_prescale(a, s)))
-            return leave(rc == NFEC_ENOTSUP && b0 == 0 ? rc : fail(rc, "tmvp prescale"));
-        queued = true;
-        if ((rc = c->tw ? launch_gf16_tw_multi(e, 3, s) : launch_gf16_t3_multi(e, 3, s)))
-            return leave(rc == NFEC_ENOTSUP && b0 == 0 ? rc : fail(rc, "tmvp products"));
-        if ((rc = launch_tmvp_postscale(a, s))) return leave(fail(rc, "tmvp postscale"));
-    }
-    return leave(NFEC_OK);
-}
-
-// the runtime-coefficient kernel's arguments of an RS8 / MDP batch encode (vec_bytes: the whole
-// vector; the callers split it into the 8-byte pieces and the tail); false: no table
-static bool rt_encode_args(const nfec_codec* c, const nfec_block_batch* b, Rs8RtArgs& a)
-{
-    if (!c->d_rt.p) return false;
-    const bool mdp = c->kind == NFEC_MDP;
-    a = Rs8RtArgs();
-    a.in_base = static_cast<const uint8_t*>(b->blocks);
-    a.in_block_stride = b->block_stride;
-    a.in_seg_stride = b->seg_stride;
-    a.out_base = static_cast<uint8_t*>(b->blocks);
-    a.out_block_stride = b->block_stride;
-    a.out_seg_stride = b->seg_stride;
-    a.nblocks = b->nblocks;
-    a.vec_bytes = c->vec;
-    a.k = c->k;
-    a.m = c->m;
-    a.tab = c->d_rt.p;
-    a.tab_col_stride = rs8_rt_col_stride(c->m);
-    a.accumulate = (b->flags & NFEC_ACCUMULATE) ? 1u : 0u;
-    if (b->num_data) {
-        // RS8: flat, each lane's blocks stopping at their own numData (the generator's columns
-        // are the same for every numData); MDP: per block, its table depends on numData
-        a.per_block = mdp ? 1 : 0;
-        a.num_data = b->num_data;
-        a.out_after_data = 1;
-        if (mdp) {
-            a.tab_block_stride = c->rt_block_bytes;
-            a.tab_by_count = 1;
-        }
-    } else {
-        a.out_slot0 = c->k;
-        if (mdp) a.tab = c->d_rt.p + (uint64_t)(c->k - 1) * (c->rt_block_bytes / 2);
-    }
-    return true;
-}
-
-// the last vec % 8 bytes of an encode whose 8-byte pieces a fast kernel took (kernels_gf8tail.hip)
-static int launch_encode_tail(const Rs8RtArgs& a, uint32_t vec, hipStream_t s)
-{
-    const int rc = launch_rs8_rt_tail(a, vec & ~7u, vec & 7u, s);
-    return rc == NFEC_OK ? NFEC_OK : fail(rc == NFEC_ENOTSUP ? NFEC_EDEVICE : rc, "encode tail launch failed");
-}
-
-// RS8 / MDP encode on the runtime-coefficient kernel (gen_rs8_rt.hip) over the vector's 8-byte
-// pieces, then (vec % 8 != 0, tail set) its last 1-7 bytes on the tail kernel with the same
-// arguments; NFEC_ENOTSUP, before anything is launched, for layouts they do not take (offsets
-// past 2^31, unaligned batches)
-int launch_rt_encode(nfec_codec* c, const nfec_block_batch* b, hipStream_t s, bool& tail)
-{
-    static const bool use_rt = diag_knob("NFEC_RT", 1) != 0;  // 0: the v_perm kernel (A/B)
-    Rs8RtArgs a;
-    if (!use_rt || !rt_encode_args(c, b, a)) return NFEC_ENOTSUP;
-    const uint32_t vec8 = c->vec & ~7u, nt = c->vec & 7u;
-    if (nt && !rs8_rt_tail_covers(a, vec8, nt)) return NFEC_ENOTSUP;
-    if (vec8) {
-        Rs8RtArgs a8 = a;
-        a8.vec_bytes = vec8;
-        const int rc = launch_rs8_rt(a8, s);
-        if (rc != NFEC_OK) return rc;
-    }
-    if (!nt) return NFEC_OK;
-    tail = true;
-    return launch_encode_tail(a, c->vec, s);
-}
-
-static int encode_device_impl(nfec_codec* c, const nfec_block_batch* b, hipStream_t s, int& path, bool& tail)
-{
-    const bool acc = b->flags & NFEC_ACCUMULATE;
-    // RS8 / MDP vectors of any length: the fast kernels over the 8-byte pieces (vec8 bytes), the
-    // tail kernel over the last nt bytes from the runtime-coefficient table every such codec has
-    // (tail_ok: it takes this batch; else the batch keeps the kernels that take whole vectors)
-    const uint32_t vec8 = c->vec & ~7u, nt = c->vec & 7u;
-    Rs8RtArgs ta;
-    const bool tail_ok = nt && vec8 && c->kind != NFEC_RS16 && rt_encode_args(c, b, ta) && rs8_rt_tail_covers(ta, vec8, nt);
-    if (c->kind == NFEC_RS8 && !force_generic()) {
-        // bit-sliced kernel specialised to this (k, m) generator, when one was generated
-        bs::EncArgs e;
-        e.base = static_cast<const uint8_t*>(b->blocks);
-        e.out = static_cast<uint8_t*>(b->blocks);
-        e.block_stride = b->block_stride;
-        e.seg_stride = b->seg_stride;
-        e.nblocks = b->nblocks;
-        e.vec = c->vec;
-        e.num_data = b->num_data;
-        e.accumulate = acc;
-        e.xcd_remap = bs_flags() & 1u;
-        e.nt_store = (bs_flags() >> 1) & 1u;
-        // hand-allocated assembly kernels first (NFEC_ASM=0 disables them for A/B runs): the
-        // 4-role-wave kernels sharing each column's transpose, then the 2-role kernels
-        if (use_asm() && use_q4() && (!nt || tail_ok)) {
-            path = NFEC_PATH_FIXED;
-            e.vec = vec8;
-            // (64, 32): the 2-role-wave kernel at 3 waves per SIMD (rs8_enc_d2.hip) for the layouts it
-            // takes, every other shape and layout the 4-role-wave kernels (NFEC_ENC_D2=0, diagnostic
-            // library: off; read per call, so one process can run both)
-            const bool use_d2 = diag_knob("NFEC_ENC_D2", 1) != 0;
-            int rc = NFEC_ENOTSUP;
-#ifdef NFEC_DIAG
-            if (use_d2) rc = launch_rs8_d2_probe(c->k, c->m, e, s);  // NFEC_D2_VARIANT: a timing probe
-#endif
-            if (rc == NFEC_ENOTSUP && use_d2) rc = launch_rs8_d2_encode(c->k, c->m, e, s);
-            if (rc == NFEC_ENOTSUP) rc = launch_rs8_q4_encode(c->k, c->m, e, s);
-            e.vec = c->vec;
-            if (rc != NFEC_ENOTSUP) {
-                if (rc != NFEC_OK) return fail(rc, "fixed-generator encode launch failed");
-                if (!nt) return NFEC_OK;
-                tail = true;
-                return launch_encode_tail(ta, c->vec, s);
-            }
-        }
-#ifdef NFEC_DIAG
-        if (use_asm()) {
-            const int rc = launch_rs8_asm_encode(c->k, c->m, e, s);
-            if (rc != NFEC_ENOTSUP) return rc == NFEC_OK ? NFEC_OK : fail(rc, "assembly encode launch failed");
-        }
-#endif
-        path = NFEC_PATH_FIXED;
-        const int rc = launch_rs8_bitsliced_encode(c->k, c->m, e, s);
-        if (rc != NFEC_ENOTSUP) return rc == NFEC_OK ? NFEC_OK : fail(rc, "bit-sliced encode launch failed");
-    }
-    if (c->kind == NFEC_RS8 && !force_generic()) {
-        // any other shape, and shortened batches (per-block mode: the block's numData columns,
-        // parity at slot numData + r): bit-sliced with runtime coefficients
-        path = NFEC_PATH_RUNTIME;
-        const int rc = launch_rt_encode(c, b, s, tail);
-        if (rc != NFEC_ENOTSUP) return rc;
-    }
-    path = NFEC_PATH_GENERIC;
-    if (c->kind == NFEC_RS8) {
-        Gf8MatmulArgs a;
-        a.in_base = static_cast<const uint8_t*>(b->blocks);
-        a.in_block_stride = b->block_stride;
-        a.in_seg_stride = b->seg_stride;
-        a.in_count = b->num_data;
-        a.cols_const = c->k;
-        a.out_base = static_cast<uint8_t*>(b->blocks);
-        a.out_block_stride = b->block_stride;
-        a.out_seg_stride = b->seg_stride;
-        a.out_slot_mode = OUT_SLOT_AFTER_INPUT;
-        a.rows_const = c->m;
-        a.coef = c->d_coef.p;
-        a.coef_col_stride = c->cs;
-        a.vtab = c->d_vtab.p;
-        a.nblocks = b->nblocks;
-        a.vec_bytes = c->vec;
-        a.accumulate = acc;
-        return launch_gf8_matmul(a, true, s);
-    }
-    if (c->kind == NFEC_RS16) {
-        static const bool use_bs16 = diag_knob("NFEC_GF16_BS", 1) != 0;
-        // (shortened batches: on the tower kernel, whose products mask each block's source
-        // slots at its numData; the prescale masks them too and the postscale writes slot
-        // numData + r)
-        if (c->tmvp && !acc && (!b->num_data || c->tw)) {
-            path = NFEC_PATH_RS16_SPLIT;
-            const int rc = rs16_tmvp_encode(c, b, s);
-            if (rc != NFEC_ENOTSUP) return rc;
-        }
-        if (c->tw || (c->d_t3off.p && !b->num_data)) {
-            // the tower kernel takes shortened batches (numData masking per 8-byte piece, parity at
-            // slot numData + r) and any even vector size (tail kernel); the shared-table kernel
-            // unshortened batches with vec % 8 = 0 only
-            Gf16T3Args t;
-            t.base = static_cast<const uint8_t*>(b->blocks);
-            t.block_stride = b->block_stride;
-            t.seg_stride = b->seg_stride;
-            t.nblocks = b->nblocks;
-            t.num_data = c->tw ? b->num_data : nullptr;
-            t.k = c->k;
-            t.m = c->m;
-            t.m_pad = gf16_t3_rows_padded(c->m);
-            t.vec_bytes = c->vec & ~1u;
-            t.offs = c->d_t3off.p;
-            t.tw = c->d_twoff.p;
-            t.accumulate = acc;
-            path = NFEC_PATH_RS16_PRODUCT;
-            const int rc = !c->tw ? launch_rs16_product(c, t, s)
-                           : rs16_tw_full_covers(t) ? launch_rs16_tw_full(t, s) : NFEC_ENOTSUP;
-            if (rc != NFEC_ENOTSUP) return rc;
-        }
-        path = NFEC_PATH_GENERIC;
-        if (use_bs16 && c->d_sel16.p) {
-            Gf16BsEncArgs e;
-            e.base = static_cast<const uint8_t*>(b->blocks);
-            e.out_base = static_cast<uint8_t*>(b->blocks);
-            e.block_stride = b->block_stride;
-            e.seg_stride = b->seg_stride;
-            e.nblocks = b->nblocks;
-            e.num_data = b->num_data;
-            e.k = c->k;
-            e.m = c->m;
-            e.vec_bytes = c->vec & ~1u;
-            e.chunks = (e.vec_bytes + 63) / 64;
-            e.sel = c->d_sel16.p;
-            e.m_pad = gf16_bs_rows_padded(c->m);
-            e.accumulate = acc;
-            const int rc = launch_gf16_bs_encode(e, s);
-            if (rc != NFEC_ENOTSUP) return rc;
-        }
-        Gf16MatmulArgs a;
-        a.in_base = static_cast<const uint8_t*>(b->blocks);
-        a.in_block_stride = b->block_stride;
-        a.in_seg_stride = b->seg_stride;
-        a.in_count = b->num_data;
-        a.cols_const = c->k;
-        a.out_base = static_cast<uint8_t*>(b->blocks);
-        a.out_block_stride = b->block_stride;
-        a.out_seg_stride = b->seg_stride;
-        a.out_slot_mode = OUT_SLOT_AFTER_INPUT;
-        a.rows_const = c->m;
-        a.coef = reinterpret_cast<const uint16_t*>(c->d_coef.p);
-        a.coef_col_stride = c->cs;
-        a.exp_tab = reinterpret_cast<const uint16_t*>(c->d_exp.p);
-        a.log_tab = c->d_log.p;
-        a.nblocks = b->nblocks;
-        a.vec_bytes = c->vec & ~1u;
-        a.accumulate = acc;
-        return launch_gf16_matmul(a, s);
-    }
-    // MDP: the in-order LFSR is a linear map of the block; the caller's parity buffers are
-    // zeroed at block start by contract, so accumulate has no reference meaning.
-    if (acc) return fail(NFEC_ENOTSUP, "MDP encode does not accumulate (LFSR restarts from zeroed parity)");
-    if (!b->num_data && use_asm() && !force_generic()) {
-        // full blocks: the LFSR's block map is a constant matrix, folded into the bit-sliced
-        // assembly bodies of the RS8 encode
-        bs::EncArgs e;
-        e.base = static_cast<const uint8_t*>(b->blocks);
-        e.out = static_cast<uint8_t*>(b->blocks);
-        e.block_stride = b->block_stride;
-        e.seg_stride = b->seg_stride;
-        e.nblocks = b->nblocks;
-        e.vec = c->vec;
-        e.num_data = nullptr;
-        e.accumulate = 0;
-        e.xcd_remap = bs_flags() & 1u;
-        e.nt_store = (bs_flags() >> 1) & 1u;
-        if (use_q4() && (!nt || tail_ok)) {
-            path = NFEC_PATH_FIXED;
-            e.vec = vec8;
-            const int rc = launch_mdp_q4_encode(c->k, c->m, e, s);
-            e.vec = c->vec;
-            if (rc != NFEC_ENOTSUP) {
-                if (rc != NFEC_OK) return fail(rc, "MDP q4 encode launch failed");
-                if (!nt) return NFEC_OK;
-                tail = true;
-                return launch_encode_tail(ta, c->vec, s);
-            }
-        }
-#ifdef NFEC_DIAG
-        const int rc = launch_mdp_asm_encode(c->k, c->m, e, s);
-        if (rc != NFEC_ENOTSUP) return rc == NFEC_OK ? NFEC_OK : fail(rc, "MDP assembly encode launch failed");
-#endif
-    }
-    if (!force_generic()) {
-        // other shapes and shortened blocks (the block map of each block length as a table)
-        path = NFEC_PATH_RUNTIME;
-        const int rc = launch_rt_encode(c, b, s, tail);
-        if (rc != NFEC_ENOTSUP) return rc;
-    }
-    path = NFEC_PATH_GENERIC;
-    Gf8MatmulArgs a;
-    a.in_base = static_cast<const uint8_t*>(b->blocks);
-    a.in_block_stride = b->block_stride;
-    a.in_seg_stride = b->seg_stride;
-    a.in_count = b->num_data;
-    a.cols_const = c->k;
-    a.out_base = static_cast<uint8_t*>(b->blocks);
-    a.out_block_stride = b->block_stride;
-    a.out_seg_stride = b->seg_stride;
-    a.out_slot_mode = OUT_SLOT_AFTER_INPUT;
-    a.rows_const = c->m;
-    a.coef = c->d_coef.p;
-    a.coef_block_stride = (uint64_t)c->k * c->cs;
-    a.coef_col_stride = c->cs;
-    a.coef_by_count = 1;
-    a.vtab = c->d_vtab.p;
-    a.nblocks = b->nblocks;
-    a.vec_bytes = c->vec;
-    return launch_gf8_matmul(a, false, s);
-}
-
-// counts each batch encode by the path that took it (nfec_codec_encode_paths)
-int encode_device(nfec_codec* c, const nfec_block_batch* b, hipStream_t s)
-{
-    int path = NFEC_PATH_GENERIC;
-    bool tail = false;
-    const int rc = encode_device_impl(c, b, s, path, tail);
-    if (rc == NFEC_OK) c->enc_paths[path].fetch_add(1, std::memory_order_relaxed);
-    if (rc == NFEC_OK && tail) c->tail_batches[0].fetch_add(1, std::memory_order_relaxed);
-    return rc;
-}
-
-// ---- RS16 decode on the tower kernel, every block ----
-// The reference replaces each erased source row of its decoding matrix by the generator row of
-// the next surviving parity (normEncoderRS16.cpp:658-716; shortened blocks :675-693) and applies
-// the inverse's erased rows (:726-753).  Here, per block, with P_t the substitute parity rows
-// and P_last the last of them:
-//   stage 1 (flat, the encode itself): z_r = parity row r ^ sum_{c < nd} G[r][c] d_c for every
-//           r <= P_last of any block (rows_lim = the batch's largest P_last + 1), with the erased
-//           source read as zero (the plan zeroes it) -- so z_{P_t} = sum_s G[P_t][E_s] d_{E_s};
-//           shortened blocks mask their columns at numData per 8-byte piece and read their
-//           parity at slot numData + r;
-//   stage 2 (per block): d_E = A^-1 z over the block's z rows 0..P_last, the inverse laid out by
-//           parity row (columns of lost parity rows are zero), written over the erased source.
-// With NFEC_ACCUMULATE the erased source is not zeroed: stage 1 then reads its contents X and
-// z = A (d_E ^ X), so stage 2's A^-1 z = d_E ^ X written over X is the reference's XOR.  Lost
-// parity (uniform loss), shortened blocks, accumulate and any even vector size (the tail kernel)
-// all run here; the round-2 exp-table kernel is left for layouts past the tower kernel's 2^31
-// offsets and codecs on the shared-table kernel.
-static bool rs16_twdec_covers(const nfec_codec* c, const nfec_block_batch* b)
-{
-    static const bool on = diag_knob("NFEC_RS16_TWDEC", 1) != 0;
-    if (!on || c->kind != NFEC_RS16 || !c->tw || !c->d_lwp.p || std::min(c->k, c->m) > kPlanCfMaxE) return false;
-    const uint32_t zstride = round_up(c->vec, 8);
-    Gf16T3Args t1;  // stage 1's layout (one block: the bounds do not depend on the count)
-    t1.base = static_cast<const uint8_t*>(b->blocks);
-    t1.block_stride = b->block_stride;
-    t1.seg_stride = b->seg_stride;
-    t1.nblocks = 1;
-    t1.num_data = b->num_data;
-    t1.k = c->k;
-    t1.m = c->m;
-    t1.vec_bytes = c->vec & ~1u;
-    t1.tw = c->d_twoff.p;
-    t1.accumulate = 1;
-    t1.out_base = reinterpret_cast<uint8_t*>(16);  // (any non-null: the z rows' layout)
-    t1.out_block_stride = (uint64_t)c->m * zstride;
-    t1.out_seg_stride = zstride;
-    t1.acc_base = t1.base;
-    t1.acc_block_stride = b->block_stride;
-    t1.acc_seg_stride = b->seg_stride;
-    t1.acc_slot0 = b->num_data ? 0u : c->k;
-    t1.acc_after_data = b->num_data ? 1u : 0u;
-    // stage 2 writes 32-bit row offsets (erased slot * seg_stride)
-    return rs16_tw_full_covers(t1) && (uint64_t)(c->k + c->m) * b->seg_stride + c->vec < (1ull << 31);
-}
-
-static int decode_rs16_tw(nfec_codec* c, const nfec_block_batch* b, const uint16_t* locs, uint32_t lstride,
-                          const uint16_t* counts, int32_t* status, hipStream_t s)
-{
-    const bool acc = b->flags & NFEC_ACCUMULATE;
-    const uint32_t zstride = round_up(c->vec, 8);
-    const uint32_t M2 = std::min(c->k, c->m);              // erased source rows at most
-    const uint32_t dcs = round_up(std::max(1u, M2), kRowPad);
-    const uint64_t zblk = (uint64_t)c->m * zstride;        // z rows 0..m-1
-    const uint64_t c2blk = (uint64_t)c->m * dcs;           // inverse by parity row: [m][dcs]
-    const size_t tw2_elems = gf16_tw_table_elems(c->m, M2);  // stage-2 table: m columns, M2 rows
-    const uint64_t per_block = zblk + 2ull * c2blk + 2ull * tw2_elems + 4ull * (M2 + 12) + 2ull * c->k + 64;
-    uint32_t cap = std::min(b->nblocks, sub_batch(per_block, 8ull << 30, 65536u));
-    const uint64_t held = c->w_z.n + c->w_coef2.n + 2ull * c->w_tw2.n;
-    if ((uint64_t)cap * per_block > held) {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-            cap = std::min(cap, sub_batch(per_block, ((uint64_t)free_b + held) / 2, 65536u));
-        else
-            (void)hipGetLastError();
-    }
-    const uint32_t npass = (b->nblocks + cap - 1) / std::max(cap, 1u);
-    const uint32_t sb = std::max(1u, (b->nblocks + npass - 1) / std::max(npass, 1u));
-    int rc;
-    if ((rc = c->w_rows.reserve(sb))) return rc;
-    if ((rc = c->w_rows1.reserve(sb))) return rc;
-    if ((rc = c->w_cols.reserve(sb))) return rc;
-    if ((rc = c->w_rmax.reserve(1))) return rc;
-    if (!status && (rc = c->w_status.reserve(sb))) return rc;
-    if ((rc = c->w_oslots.reserve((size_t)sb * c->k + 128))) return rc;
-    if ((rc = c->w_z.reserve((size_t)sb * zblk))) return rc;
-    if ((rc = c->w_coef2.reserve((size_t)sb * c2blk * 2))) return rc;
-    if ((rc = c->w_tw2.reserve((size_t)sb * tw2_elems))) return rc;
-    if ((rc = c->w_rowoff.reserve((size_t)sb * (M2 + 12)))) return rc;
-    uint16_t phi[16];
-    uint32_t lam = 0;
-    gf16_tw_field(phi, &lam);
-    for (uint32_t b0 = 0; b0 < b->nblocks; b0 += sb) {
-        const uint32_t nb = std::min(sb, b->nblocks - b0);
-        uint8_t* blocks = static_cast<uint8_t*>(b->blocks) + (uint64_t)b0 * b->block_stride;
-        const uint16_t* nd = b->num_data ? b->num_data + b0 : nullptr;
-        int32_t* st = status ? status + b0 : c->w_status.p;
-        NFEC_HIP(hipMemsetAsync(c->w_rmax.p, 0, sizeof(uint32_t), s));
-        RsPlanArgs p;
-        p.bits = 16;
-        p.k = c->k;
-        p.m = c->m;
-        p.nblocks = nb;
-        p.num_data = nd;
-        p.erasure_locs = locs + (uint64_t)b0 * lstride;
-        p.erasure_stride = lstride;
-        p.erasure_counts = counts + b0;
-        p.gen_parity = c->d_gen.p;
-        p.exp_tab = c->d_exp.p;
-        p.log_tab = c->d_log.p;
-        p.status = st;
-        p.rows = c->w_rows.p;
-        p.out_slots2 = c->w_oslots.p;
-        p.cols2 = c->w_cols.p;
-        p.coef_stride = dcs;
-        p.coef2 = c->w_coef2.p;
-        p.coef2_block = c2blk;
-        p.lwp = c->d_lwp.p;
-        p.lw = c->d_lw.p;
-        p.by_row = 1;
-        p.rows1 = c->w_rows1.p;
-        p.rmax = c->w_rmax.p;
-        p.zero_base = acc ? nullptr : blocks;
-        p.zero_block_stride = b->block_stride;
-        p.zero_seg_stride = b->seg_stride;
-        p.zero_vec = c->vec & ~1u;
-        if ((rc = launch_rs_plan(p, s))) return rc;
-        // stage 1: z rows 0..rows_lim-1 of every block by the encode, XORed with its parity rows
-        Gf16T3Args t;
-        t.base = blocks;
-        t.block_stride = b->block_stride;
-        t.seg_stride = b->seg_stride;
-        t.nblocks = nb;
-        t.num_data = nd;
-        t.k = c->k;
-        t.m = c->m;
-        t.vec_bytes = c->vec & ~1u;
-        t.tw = c->d_twoff.p;
-        t.accumulate = 1;
-        t.out_base = c->w_z.p;
-        t.out_block_stride = zblk;
-        t.out_seg_stride = zstride;
-        t.out_slot0 = 0;
-        t.acc_base = blocks;
-        t.acc_block_stride = b->block_stride;
-        t.acc_seg_stride = b->seg_stride;
-        t.acc_slot0 = nd ? 0u : c->k;
-        t.acc_after_data = nd ? 1u : 0u;
-        t.rows_lim = c->w_rmax.p;
-        if ((rc = launch_rs16_tw_full(t, s))) return rc == NFEC_ENOTSUP ? fail(NFEC_EDEVICE, "tower decode stage 1") : rc;
-        // stage 2: the per-block tables of A^-1 by parity row, then d_E = A^-1 z
-        TwDecTablesArgs d;
-        d.coef2 = reinterpret_cast<const uint16_t*>(c->w_coef2.p);
-        d.dcs = dcs;
-        d.coef2_block = c2blk;
-        d.rows = c->w_rows.p;
-        d.cols = c->w_cols.p;
-        d.out_slots = c->w_oslots.p;
-        d.slots_stride = c->k;
-        d.seg_stride = b->seg_stride;
-        d.nblocks = nb;
-        d.M = M2;
-        d.tw = c->w_tw2.p;
-        d.tw_block_stride = tw2_elems;
-        d.row_off = c->w_rowoff.p;
-        std::copy(phi, phi + 16, d.phi);
-        d.lam = lam;
-        if ((rc = launch_tw_dec_tables(d, s))) return rc;
-        Gf16T3Args t2;
-        t2.base = c->w_z.p;
-        t2.block_stride = zblk;
-        t2.seg_stride = zstride;
-        t2.nblocks = nb;
-        t2.k = c->m;   // columns: z rows 0..P_last (blk_cols)
-        t2.m = M2;     // rows: the block's e erased source (blk_rows)
-        t2.vec_bytes = c->vec & ~1u;
-        t2.tw = c->w_tw2.p;
-        t2.tw_block_stride = tw2_elems;
-        t2.blk_rows = c->w_rows.p;
-        t2.blk_cols = c->w_cols.p;
-        t2.row_off = c->w_rowoff.p;
-        t2.row_off_stride = M2 + 12;
-        t2.out_base = blocks;
-        t2.out_block_stride = b->block_stride;
-        t2.out_seg_stride = b->seg_stride;
-        if ((rc = launch_rs16_tw_full(t2, s))) return rc == NFEC_ENOTSUP ? fail(NFEC_EDEVICE, "tower decode stage 2") : rc;
-    }
-    return NFEC_OK;
-}
-
-// ---- decode on a device batch ----
-// caller_locked: the caller already holds c->mu (nfec_decode_vectors keeps it for the whole
-// per-call decode, staging included)
-static int decode_device_impl(nfec_codec* c, const nfec_block_batch* b, const uint16_t* locs, uint32_t lstride,
-                              const uint16_t* counts, int32_t* status, hipStream_t s, bool caller_locked, int& path,
-                              bool& tail)
-{
-    if (!locs || !counts) return fail(NFEC_EINVAL, "null erasure arrays");
-    const bool acc = b->flags & NFEC_ACCUMULATE;
-    if (c->kind == NFEC_MDP && acc) return fail(NFEC_ENOTSUP, "MDP decode requires zero-filled erased segments");
-    std::unique_lock<std::mutex> lk(c->mu, std::defer_lock);
-    if (!caller_locked) lk.lock();
-    if (rs16_twdec_covers(c, b)) {
-        path = NFEC_DPATH_RS16_TOWER;
-        return decode_rs16_tw(c, b, locs, lstride, counts, status, s);
-    }
-    const uint32_t n = c->k + c->m;
-    const uint32_t zstride = round_up(c->vec, 8);
-    // RS decode rows: at most min(k, m) source erasures are solved per block, so the plan's
-    // matrices and the z rows are sized by that, not by m (m >> k codes, e.g. npc's auto mode)
-    const uint32_t dcs = c->kind == NFEC_MDP ? c->cs : round_up(std::max(1u, std::min(c->k, c->m)), kRowPad);
-    const bool big_plan = c->kind != NFEC_MDP && std::min(c->k, c->m) > 64;
-    // RS8 blocks the fused / fixed-shape kernels do not take: a closed-form plan writes each
-    // block's whole repair map (e x numData, rs8_plan_rt_kernel) as a pass-major snippet table
-    // (8 rows per pass, 16 bytes per column) and ONE pass of the runtime-coefficient kernel
-    // computes the erased source from the received columns
-    // (NFEC_RT_DEC=1: the one-pass runtime-coefficient repair for those shapes too, for A/B)
-    static const bool rt_first = diag_knob("NFEC_RT_DEC", 0) != 0;
-    // (shortened batches too: the plan marks each block's columns past its numData like erased
-    // ones, and the repair kernels read its parity at slot numData + t)
-    const bool fast = !rt_first && c->kind == NFEC_RS8 && c->m <= 32 && c->k <= 64 && !force_generic() &&
-                      has_bitsliced(c->k, c->m) && bs::offsets_fit(b->block_stride, b->seg_stride);
-    static const bool use_rt = diag_knob("NFEC_RT", 1) != 0;
-    // RS8 / MDP vectors of any length: the bit-sliced repair kernels over the 8-byte pieces (vec8
-    // bytes), the tail kernels (kernels_gf8tail.hip) over the last nt bytes.  They read a column's
-    // tail as 8 aligned bytes inside its slot (tail_layout; nfec.h asks for this layout anyway); a
-    // batch without it keeps the kernels that take whole vectors
-    const uint32_t vec8 = c->vec & ~7u, nt = c->kind == NFEC_RS16 ? 0u : c->vec & 7u;
-    const bool tail_layout = nt && (reinterpret_cast<uintptr_t>(b->blocks) & 7u) == 0 && (b->block_stride & 7u) == 0 &&
-                             (b->seg_stride & 7u) == 0 && (uint64_t)vec8 + 8u <= b->seg_stride;
-    const bool rt_dec = use_rt && !fast && c->kind == NFEC_RS8 && (!nt || tail_layout) && c->d_rt.p && c->d_lwp.p &&
-                        !force_generic() &&
-                        b->block_stride + (uint64_t)(c->k + c->m) * b->seg_stride + c->vec < (1ull << 31);
-    const uint32_t E = std::min(c->k, c->m);
-    // (+ RS16 on the tower kernel: stage 2's per-block snippet tables and row offsets)
-    // MDP repair on the runtime-coefficient kernel (the plan's matrix as snippet offsets, one
-    // pass over the survivors), else the snippet solve / generic kernel (NFEC_MDP_RT=0)
-    static const bool use_mdp_rt = diag_knob("NFEC_MDP_RT", 1) != 0;
-    const uint32_t mdp_np = rs8_rt_passes(std::min(c->k, c->m));  // passes of its pass-major table
-    auto mdp_rt_args = [&](uint8_t* blocks, uint32_t nb) {
-        Rs8RtArgs r;
-        r.in_base = blocks;
-        r.in_block_stride = b->block_stride;
-        r.in_seg_stride = b->seg_stride;
-        r.out_base = blocks;
-        r.out_block_stride = b->block_stride;
-        r.out_seg_stride = b->seg_stride;
-        r.nblocks = nb;
-        r.vec_bytes = vec8;
-        r.k = n;                          // columns: the block's survivors, up to k + m
-        r.m = std::min(c->k, c->m);       // rows: its erased source
-        r.per_block = 1;
-        r.blk_cols = c->w_cols.p;
-        r.blk_rows = c->w_rows.p;
-        r.in_slots = c->w_islots.p;
-        r.in_slots_stride = n;
-        r.out_slots = c->w_oslots.p;
-        r.out_slots_stride = n;
-        r.tab = reinterpret_cast<const uint16_t*>(c->w_coef1.p);
-        r.tab_block_stride = (uint64_t)mdp_np * n * 16;
-        r.tab_col_stride = 16;
-        r.tab_pass_stride = (uint64_t)n * 16;
-        r.slot_bound = n;
-        return r;
-    };
-    // (the layout is probed before the workspace exists: any non-null table stands in for it, so a
-    // codec's first batch takes the same path as its later ones)
-    auto mdp_rt_layout = [&]() {
-        Rs8RtArgs r = mdp_rt_args(static_cast<uint8_t*>(b->blocks), 1);
-        if (!r.tab) r.tab = c->d_rt.p;
-        return (vec8 == 0 || rs8_rt_covers(r)) && (nt == 0 || rs8_rt_tail_covers(r, vec8, nt));
-    };
-    const bool mdp_rt = c->kind == NFEC_MDP && use_mdp_rt && (!nt || tail_layout) && !force_generic() && mdp_rt_layout();
-    path = fast ? NFEC_DPATH_FIXED : (rt_dec || mdp_rt) ? NFEC_DPATH_RUNTIME : NFEC_DPATH_GENERIC;
-    const uint32_t rt_np = rs8_rt_passes(std::min(c->k, c->m));  // RS8 repair table passes
-    const uint64_t ws_per_block = c->kind == NFEC_MDP ? (mdp_rt ? (uint64_t)mdp_np * n * 16 : (uint64_t)n * c->cs)
-                                  : rt_dec            ? (uint64_t)rt_np * c->k * 16
-                                                      : (uint64_t)dcs * zstride + ((uint64_t)c->k + dcs) * dcs * c->sym +
-                                                 (big_plan ? rs_plan_work_bytes(dcs, c->sym) : 0) +
-                                                 (c->tw ? 2ull * gf16_tw_table_elems(E, E) + 4ull * (E + 12) : 0);
-    // the runtime-coefficient repair takes passes of up to 1M blocks (its launches stay well
-    // below the grid limits): small codes, many blocks, no per-pass launch and plan overhead
-    const uint32_t max_pass = rt_dec ? (1u << 20) : 65536u;
-    // passes of equal size, so no launch runs a small tail batch
-    // passes as large as 8 GiB of workspace allows; when that would grow the workspace past what
-    // the codec holds, also within half of the device memory free now (plus what it holds), so
-    // a smaller GPU or several codecs per device get smaller passes instead of NFEC_ENOMEM
-    const uint64_t per_block = ws_per_block + 4ull * n + 64;
-    uint32_t cap = std::min(b->nblocks, sub_batch(per_block, 8ull << 30, max_pass));
-    const uint64_t held = c->w_z.n + c->w_coef1.n + c->w_coef2.n + c->w_work.n + 2ull * c->w_tw2.n;
-    if ((uint64_t)cap * per_block > held) {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-            cap = std::min(cap, sub_batch(per_block, ((uint64_t)free_b + held) / 2, max_pass));
-        else
-            (void)hipGetLastError();
-    }
-    const uint32_t npass = (b->nblocks + cap - 1) / std::max(cap, 1u);
-    const uint32_t sb = std::max(1u, (b->nblocks + npass - 1) / std::max(npass, 1u));
-    int rc;
-    if ((rc = c->w_rows.reserve(sb))) return rc;
-    if ((rc = c->w_cols.reserve(sb))) return rc;
-    if (!status && (rc = c->w_status.reserve(sb))) return rc;
-    // + 128: the bit-sliced solves' scalar loads read up to 128 slots past a block's list
-    if ((rc = c->w_islots.reserve((size_t)sb * n + 128))) return rc;
-    if ((rc = c->w_oslots.reserve((size_t)sb * n + 128))) return rc;
-    if (c->kind == NFEC_MDP) {
-        if ((rc = c->w_coef1.reserve(mdp_rt ? (size_t)sb * mdp_np * n * 16 + 128 : (size_t)sb * n * dcs))) return rc;
-    } else if (rt_dec) {
-        if ((rc = c->w_coef1.reserve((size_t)sb * rt_np * c->k * 16 + 128))) return rc;
-    } else {
-        if ((rc = c->w_coef1.reserve((size_t)sb * c->k * dcs * c->sym))) return rc;
-        if ((rc = c->w_coef2.reserve((size_t)sb * dcs * dcs * c->sym))) return rc;
-        if ((rc = c->w_z.reserve((size_t)sb * dcs * zstride))) return rc;
-        if (big_plan && (rc = c->w_work.reserve((size_t)sb * rs_plan_work_bytes(dcs, c->sym)))) return rc;
-    }
-    // RS16 stage 1 by the shared-table encode for the blocks whose substitute parities are rows
-    // 0..e-1 (RsPlanArgs::rows1): overwrite semantics only, since it zeroes the erased source
-    // z_t = (encode row t of the block, erased source zeroed) ^ received parity t
-    auto t3_stage1 = [&](uint8_t* blocks, uint32_t nb) {
-        Gf16T3Args t;
-        t.base = blocks;
-        t.block_stride = b->block_stride;
-        t.seg_stride = b->seg_stride;
-        t.nblocks = nb;
-        t.k = c->k;
-        t.m = c->m;
-        t.m_pad = gf16_t3_rows_padded(c->m);
-        t.vec_bytes = c->vec & ~1u;
-        t.offs = c->d_t3off.p;
-        t.tw = c->d_twoff.p;
-        t.accumulate = 1;
-        t.out_base = c->w_z.p;
-        t.out_block_stride = (uint64_t)dcs * zstride;
-        t.out_seg_stride = zstride;
-        t.out_slot0 = 0;
-        t.acc_base = blocks;
-        t.acc_block_stride = b->block_stride;
-        t.acc_seg_stride = b->seg_stride;
-        t.acc_slot0 = c->k;
-        t.rows_lim = c->w_rmax.p;
-        return t;
-    };
-    // the plan marks blocks for this stage 1 only when the kernel takes the batch's layout
-    // (t3_prepare's 2^31 offset bounds); otherwise every block keeps the gather stage
-    bool t3dec = c->kind == NFEC_RS16 && (c->d_t3off.p || c->tw) && !b->num_data && !acc && (c->vec % 8) == 0;
-    if (t3dec) {
-        const Gf16T3Args t = t3_stage1(static_cast<uint8_t*>(b->blocks), sb);
-        t3dec = c->tw ? gf16_tw_covers(t) : gf16_t3_covers(t);
-    }
-    if (t3dec) {
-        if ((rc = c->w_rows1.reserve(sb))) return rc;
-        if ((rc = c->w_rmax.reserve(1))) return rc;
-    }
-    // RS16 stage 2 (d_E = A^-1 z) on the tower kernel in per-block mode, with the batches stage
-    // 1 takes by encode (overwrite, unshortened); tables of M = min(k, m) rows per block
-    const uint32_t M2 = std::min(c->k, c->m);
-    const size_t tw2_elems = gf16_tw_table_elems(M2, M2);
-    // (the per-block row offsets are 32-bit buffer offsets of erased source slots: slot * stride)
-    const bool tw2 = t3dec && c->tw && diag_knob("NFEC_RS16_TW2", 1) != 0 &&
-                     (uint64_t)c->k * b->seg_stride + c->vec < (1ull << 31);
-    if (tw2) {
-        if ((rc = c->w_tw2.reserve((size_t)sb * tw2_elems))) return rc;
-        if ((rc = c->w_rowoff.reserve((size_t)sb * (M2 + 12)))) return rc;
-    }
-    if (fast) {
-        if ((rc = c->w_emask.reserve((size_t)sb * 2))) return rc;
-        if ((rc = c->w_psel.reserve((size_t)sb * 2))) return rc;
-        if ((rc = c->w_pmap.reserve((size_t)sb * c->m))) return rc;
-        if ((rc = c->w_gate.reserve(1))) return rc;
-    }
-    for (uint32_t b0 = 0; b0 < b->nblocks; b0 += sb) {
-        const uint32_t nb = std::min(sb, b->nblocks - b0);
-        uint8_t* blocks = static_cast<uint8_t*>(b->blocks) + (uint64_t)b0 * b->block_stride;
-        const uint16_t* nd = b->num_data ? b->num_data + b0 : nullptr;
-        const uint16_t* l = locs + (uint64_t)b0 * lstride;
-        const uint16_t* cnt = counts + b0;
-        int32_t* st = status ? status + b0 : c->w_status.p;
-        if (c->kind == NFEC_MDP) {
-            MdpPlanArgs p;
-            p.k = c->k;
-            p.m = c->m;
-            p.nblocks = nb;
-            p.num_data = nd;
-            p.erasure_locs = l;
-            p.erasure_stride = lstride;
-            p.erasure_counts = cnt;
-            p.exp_tab = c->d_exp.p;
-            p.log_tab = c->d_log.p;
-            p.status = st;
-            p.rows = c->w_rows.p;
-            p.cols = c->w_cols.p;
-            p.in_slots = c->w_islots.p;
-            p.out_slots = c->w_oslots.p;
-            p.coef_stride = dcs;
-            p.coef = c->w_coef1.p;
-            if (mdp_rt) {
-                p.coef16 = reinterpret_cast<uint16_t*>(c->w_coef1.p);
-                p.npass16 = mdp_np;
-                if ((rc = launch_mdp_plan(p, s))) return rc;
-                if (vec8 && (rc = launch_rs8_rt(mdp_rt_args(blocks, nb), s)))
-                    return fail(rc == NFEC_ENOTSUP ? NFEC_EDEVICE : rc, "MDP runtime-coefficient repair launch failed");
-                if (nt) {
-                    if ((rc = launch_rs8_rt_tail(mdp_rt_args(blocks, nb), vec8, nt, s)))
-                        return fail(rc == NFEC_ENOTSUP ? NFEC_EDEVICE : rc, "MDP repair tail launch failed");
-                    tail = true;
-                }
-                continue;
-            }
-            if ((rc = launch_mdp_plan(p, s))) return rc;
-            // blocks with <= 16 erased source vectors: the snippet solve (NFEC_MDP_BS=0: off)
-            static const bool use_mdp_bs = diag_knob("NFEC_MDP_BS", 1) != 0;
-            if (use_mdp_bs) {
-                MdpSolveArgs ms;
-                ms.base = blocks;
-                ms.block_stride = b->block_stride;
-                ms.seg_stride = b->seg_stride;
-                ms.nblocks = nb;
-                ms.vec = c->vec;
-                ms.rows = c->w_rows.p;
-                ms.cols = c->w_cols.p;
-                ms.in_slots = c->w_islots.p;
-                ms.out_slots = c->w_oslots.p;
-                ms.slots_stride = n;
-                ms.coef = c->w_coef1.p;
-                ms.coef_block_stride = (uint64_t)n * dcs;
-                ms.coef_col_stride = dcs;
-                rc = launch_mdp_solve_bs(ms, s);
-                if (rc != NFEC_OK && rc != NFEC_ENOTSUP) return fail(rc, "MDP solve launch failed");
-            }
-            Gf8MatmulArgs a;
-            a.in_base = blocks;
-            a.in_block_stride = b->block_stride;
-            a.in_seg_stride = b->seg_stride;
-            a.in_slots = c->w_islots.p;
-            a.in_count = c->w_cols.p;
-            a.out_base = blocks;
-            a.out_block_stride = b->block_stride;
-            a.out_seg_stride = b->seg_stride;
-            a.out_slots = c->w_oslots.p;
-            a.out_slot_mode = OUT_SLOT_LIST;
-            a.row_count = c->w_rows.p;
-            a.slots_stride = n;
-            a.coef = c->w_coef1.p;
-            a.coef_block_stride = (uint64_t)n * dcs;
-            a.coef_col_stride = dcs;
-            a.vtab = c->d_vtab.p;
-            a.nblocks = nb;
-            a.vec_bytes = c->vec;
-            if ((rc = launch_gf8_matmul(a, false, s))) return rc;
-            continue;
-        }
-        if (fast) {
-            // closed-form plan -> bit-sliced re-encode (z) -> e x e inverse (generic kernel)
-            RsPlan2Args p2;
-            p2.k = c->k;
-            p2.m = c->m;
-            p2.nblocks = nb;
-            p2.num_data = nd;
-            p2.erasure_locs = l;
-            p2.erasure_stride = lstride;
-            p2.erasure_counts = cnt;
-            p2.exp_tab = c->d_exp.p;
-            p2.log_tab = c->d_log.p;
-            p2.lwp = c->d_lwp.p;
-            p2.lw = c->d_lw.p;
-            p2.status = st;
-            p2.rows = c->w_rows.p;
-            p2.cols2 = c->w_cols.p;
-            p2.out_slots2 = c->w_oslots.p;
-            p2.emask = c->w_emask.p;
-            p2.psel = c->w_psel.p;
-            p2.pmap = c->w_pmap.p;
-            p2.coef_stride = dcs;
-            p2.coef2 = c->w_coef2.p;
-            // fused per-block repair for the blocks it qualifies for (NFEC_FUSED=0: off); the
-            // unfused stage 1 and solve below skip the blocks it marked
-            static const bool use_fused = diag_knob("NFEC_FUSED", 1) != 0;
-            FdecArgs f;
-            f.base = blocks;
-            f.block_stride = b->block_stride;
-            f.seg_stride = b->seg_stride;
-            f.nblocks = nb;
-            // segment tails: every kernel of this path over the 8-byte pieces, the tail kernel
-            // (after the plan, before the fused kernel clears rows / psel) over the last nt bytes
-            // of every decodable block
-            Rs8FixedDecTailArgs ft;
-            ft.base = blocks;
-            ft.block_stride = b->block_stride;
-            ft.seg_stride = b->seg_stride;
-            ft.nblocks = nb;
-            ft.k = c->k;
-            ft.m = c->m;
-            ft.num_data = nd;
-            ft.rows = c->w_rows.p;
-            ft.emask = c->w_emask.p;
-            ft.psel = c->w_psel.p;
-            ft.pmap = c->w_pmap.p;
-            ft.out_slots = c->w_oslots.p;
-            ft.slots_stride = c->k;
-            ft.coef2 = c->w_coef2.p;
-            ft.coef_stride = dcs;
-            ft.fused_rows = std::min(16u, c->m);
-            ft.gen = c->d_gen.p;
-            ft.accumulate = acc;
-            const bool split = tail_layout && rs8_fixed_dec_tail_covers(ft, vec8, nt);
-            const uint32_t fvec = split ? vec8 : c->vec;  // what the other kernels take
-            f.vec = fvec;
-            f.ips = fvec / 8;
-            f.rows = c->w_rows.p;
-            f.psel = c->w_psel.p;
-            f.emask = c->w_emask.p;
-            f.coef = c->w_coef2.p;
-            f.coef_block_stride = (uint64_t)dcs * dcs;
-            f.coef_col_stride = dcs;
-            f.out_slots = c->w_oslots.p;
-            f.slots_stride = c->k;
-            f.accumulate = acc;
-            f.num_data = nd;
-            // 2 (default) = compact lane-major items, idle lanes out of EXEC (1.981-1.985 vs
-            // 1.989-1.998 ms, r02g); 0 = item q*64 + lane; 1 = lane L holds items 4L..4L+3
-            // (strided loads: 2.16 vs 2.02 ms).  NFEC_FDEC_LANEMAJOR overrides (diagnostic library).
-            static const uint32_t lane_major = (uint32_t)diag_knob("NFEC_FDEC_LANEMAJOR", 2, 0, 2);
-            f.lane_major = lane_major;
-            const bool fused = use_fused && fvec && rs8_fused_decode_covers(c->k, c->m, f);
-            // gate: the plan writes this pass's generation into w_gate when some block needs the
-            // unfused kernels; when the fused kernel ran they skip their whole launch otherwise
-            const uint32_t gen = ++c->gate_gen;
-            if (fused) {
-                p2.gate = c->w_gate.p;
-                p2.gate_gen = gen;
-                p2.fused_rows = std::min(16u, c->m);  // the inverse of the blocks it takes, by row
-            }
-            if ((rc = launch_rs_plan2(p2, s))) return rc;
-            if (split) {
-                ft.fused_rows = p2.fused_rows;
-                if ((rc = launch_rs8_fixed_dec_tail(ft, vec8, nt, s)))
-                    return fail(rc == NFEC_ENOTSUP ? NFEC_EDEVICE : rc, "fixed-shape repair tail launch failed");
-                tail = true;
-                if (!fvec) continue;  // no 8-byte piece: the tail kernel repaired the whole vector
-            }
-            const uint32_t* gate = nullptr;
-            if (fused) {
-                // the 3-waves-per-SIMD kernel where it applies (lane-major items, segments up to
-                // 1,664 B, m = 32 or 16; NFEC_FDEC3=0: off), else the 2-waves one
-                static const bool use_fdec3 = diag_knob("NFEC_FDEC3", 1) != 0;
-                rc = use_fdec3 ? launch_rs8_fdec3(c->k, c->m, f, s) : NFEC_ENOTSUP;
-                if (rc == NFEC_ENOTSUP) rc = launch_rs8_fused_decode(c->k, c->m, f, s);
-                if (rc != NFEC_OK) return fail(rc == NFEC_ENOTSUP ? NFEC_EDEVICE : rc, "fused decode launch failed");
-                gate = c->w_gate.p;
-            }
-            bs::DecArgs d;
-            d.base = blocks;
-            d.block_stride = b->block_stride;
-            d.seg_stride = b->seg_stride;
-            d.nblocks = nb;
-            d.vec = fvec;
-            d.emask = c->w_emask.p;
-            d.psel = c->w_psel.p;
-            d.pmap = c->w_pmap.p;
-            d.z = c->w_z.p;
-            d.z_block_stride = (uint64_t)dcs * zstride;
-            d.z_stride = zstride;
-            d.xcd_remap = bs_flags() & 1u;
-            d.gate = gate;
-            d.gate_gen = gen;
-            d.num_data = nd;
-            if ((rc = launch_rs8_bitsliced_reencode(c->k, c->m, d, s))) return fail(rc, "bit-sliced re-encode launch failed");
-            static const bool use_solve = diag_knob("NFEC_SOLVE", 1) != 0;
-            if (!use_solve) {
-                Gf8MatmulArgs g2;
-                g2.in_base = c->w_z.p;
-                g2.in_block_stride = (uint64_t)dcs * zstride;
-                g2.in_seg_stride = zstride;
-                g2.in_count = c->w_cols.p;
-                g2.out_base = blocks;
-                g2.out_block_stride = b->block_stride;
-                g2.out_seg_stride = b->seg_stride;
-                g2.out_slots = c->w_oslots.p;
-                g2.out_slot_mode = OUT_SLOT_LIST;
-                g2.row_count = c->w_rows.p;
-                g2.slots_stride = c->k;
-                g2.coef = c->w_coef2.p;
-                g2.coef_block_stride = (uint64_t)dcs * dcs;
-                g2.coef_col_stride = dcs;
-                g2.vtab = c->d_vtab.p;
-                g2.nblocks = nb;
-                g2.vec_bytes = fvec;
-                g2.accumulate = acc;
-                if ((rc = launch_gf8_matmul(g2, false, s))) return rc;
-                continue;
-            }
-            Gf8SolveArgs a2;
-            a2.z = c->w_z.p;
-            a2.z_block_stride = (uint64_t)dcs * zstride;
-            a2.z_stride = zstride;
-            a2.cols = c->w_cols.p;
-            a2.rows = c->w_rows.p;
-            a2.out_slots = c->w_oslots.p;
-            a2.slots_stride = c->k;
-            a2.out = blocks;
-            a2.out_block_stride = b->block_stride;
-            a2.out_seg_stride = b->seg_stride;
-            a2.coef = c->w_coef2.p;
-            a2.coef_block_stride = (uint64_t)dcs * dcs;
-            a2.coef_col_stride = dcs;
-            a2.vtab = c->d_vtab.p;
-            a2.nblocks = nb;
-            a2.vec_bytes = fvec;
-            a2.accumulate = acc;
-            a2.gate = gate;
-            a2.gate_gen = gen;
-            // bit-sliced snippet-table solve for blocks with <= 16 erasures (NFEC_SOLVE_BS=0: off),
-            // the v_perm kernel for the rest
-            static const bool use_bs = diag_knob("NFEC_SOLVE_BS", 1) != 0;
-            if (use_bs) {
-                rc = launch_gf8_solve_bs(a2, s);
-                if (rc != NFEC_OK && rc != NFEC_ENOTSUP) return fail(rc, "bit-sliced solve launch failed");
-                if (rc == NFEC_OK) {
-                    if (std::min(c->m, c->k) > 16) {
-                        a2.min_rows = 16;
-                        if ((rc = launch_gf8_solve(a2, std::min(c->m, c->k), c->m, s))) return rc;
-                    }
-                    continue;
-                }
-            }
-            if ((rc = launch_gf8_solve(a2, std::min(c->m, c->k), c->m, s))) return rc;
-            continue;
-        }
-        RsPlanArgs p;
-        p.bits = c->kind == NFEC_RS16 ? 16 : 8;
-        p.k = c->k;
-        p.m = c->m;
-        p.nblocks = nb;
-        p.num_data = nd;
-        p.erasure_locs = l;
-        p.erasure_stride = lstride;
-        p.erasure_counts = cnt;
-        p.gen_parity = c->d_gen.p;
-        p.exp_tab = c->d_exp.p;
-        p.log_tab = c->d_log.p;
-        p.status = st;
-        p.rows = c->w_rows.p;
-        p.in_slots1 = c->w_islots.p;
-        p.out_slots2 = c->w_oslots.p;
-        p.cols2 = c->w_cols.p;
-        p.coef_stride = dcs;
-        p.coef1 = c->w_coef1.p;
-        p.coef2 = c->w_coef2.p;
-        p.work = big_plan ? c->w_work.p : nullptr;
-        p.work_block_bytes = rs_plan_work_bytes(dcs, c->sym);
-        // RS16: the closed-form inverse when every block's e fits it (NFEC_RS16_CF=0: Gauss-Jordan)
-        static const bool use_cf16 = diag_knob("NFEC_RS16_CF", 1) != 0;
-        if (c->kind == NFEC_RS16 && use_cf16 && c->d_lwp.p && std::min(c->k, c->m) <= kPlanCfMaxE) {
-            p.lwp = c->d_lwp.p;
-            p.lw = c->d_lw.p;
-        }
-        if (t3dec) {
-            NFEC_HIP(hipMemsetAsync(c->w_rmax.p, 0, sizeof(uint32_t), s));
-            p.rows1 = c->w_rows1.p;
-            p.rmax = c->w_rmax.p;
-            p.zero_base = blocks;
-            p.zero_block_stride = b->block_stride;
-            p.zero_seg_stride = b->seg_stride;
-            p.zero_vec = c->vec & ~1u;
-        }
-        if (rt_dec) {
-            // d_E (erased source slots out_slots2) = W x the block's nd received columns (slots
-            // in_slots1: the surviving source and, for an erased one, its substitute parity)
-            Rs8RtArgs r;
-            r.in_base = blocks;
-            r.in_block_stride = b->block_stride;
-            r.in_seg_stride = b->seg_stride;
-            r.out_base = blocks;
-            r.out_block_stride = b->block_stride;
-            r.out_seg_stride = b->seg_stride;
-            r.nblocks = nb;
-            r.vec_bytes = vec8;
-            r.k = c->k;
-            r.m = E;
-            r.per_block = 1;
-            r.num_data = nd;
-            r.blk_rows = c->w_rows.p;
-            r.in_slots = c->w_islots.p;
-            r.in_slots_stride = c->k;
-            r.out_slots = c->w_oslots.p;
-            r.out_slots_stride = c->k;
-            r.tab = reinterpret_cast<const uint16_t*>(c->w_coef1.p);
-            r.tab_block_stride = (uint64_t)rt_np * c->k * 16;
-            r.tab_col_stride = 16;
-            r.tab_pass_stride = (uint64_t)c->k * 16;
-            r.accumulate = acc;
-            r.slot_bound = c->k + c->m;
-            if ((vec8 && !rs8_rt_covers(r)) || (nt && !rs8_rt_tail_covers(r, vec8, nt)))
-                return fail(NFEC_ENOTSUP, "runtime-coefficient repair: batch layout past its 2^31 offsets");
-            p.lwp = c->d_lwp.p;
-            p.lw = c->d_lw.p;
-            if ((rc = launch_rs8_plan_rt(p, rt_np, s))) return rc;
-            if (vec8 && (rc = launch_rs8_rt(r, s)))
-                return fail(rc == NFEC_ENOTSUP ? NFEC_EDEVICE : rc, "runtime-coefficient repair launch failed");
-            if (nt) {
-                if ((rc = launch_rs8_rt_tail(r, vec8, nt, s)))
-                    return fail(rc == NFEC_ENOTSUP ? NFEC_EDEVICE : rc, "runtime-coefficient repair tail launch failed");
-                tail = true;
-            }
-            continue;
-        }
-        if ((rc = launch_rs_plan(p, s))) return rc;
-        if (t3dec) {
-            // z_t for t below the plan's largest such e; the gather stage then overwrites the z
-            // rows of the other blocks
-            rc = launch_rs16_product(c, t3_stage1(blocks, nb), s);
-            if (rc == NFEC_ENOTSUP) return fail(rc, "t3 decode stage 1: layout not covered");
-            if (rc) return rc;
-        }
-        // stage 1: z_t = parity(P_t) ^ sum_{present c} G[P_t][c] d_c  -> scratch rows
-        // stage 2: d_E = A^-1 z                                          -> erased slots
-        if (c->kind == NFEC_RS8) {
-            Gf8MatmulArgs a;
-            a.in_base = blocks;
-            a.in_block_stride = b->block_stride;
-            a.in_seg_stride = b->seg_stride;
-            a.in_slots = c->w_islots.p;
-            a.in_count = nd;
-            a.cols_const = c->k;
-            a.out_base = c->w_z.p;
-            a.out_block_stride = (uint64_t)dcs * zstride;
-            a.out_seg_stride = zstride;
-            a.out_slot_mode = OUT_SLOT_ROW;
-            a.row_count = c->w_rows.p;
-            a.slots_stride = c->k;
-            a.coef = c->w_coef1.p;
-            a.coef_block_stride = (uint64_t)c->k * dcs;
-            a.coef_col_stride = dcs;
-            a.vtab = c->d_vtab.p;
-            a.nblocks = nb;
-            a.vec_bytes = c->vec;
-            if ((rc = launch_gf8_matmul(a, false, s))) return rc;
-            Gf8MatmulArgs a2;
-            a2.in_base = c->w_z.p;
-            a2.in_block_stride = (uint64_t)dcs * zstride;
-            a2.in_seg_stride = zstride;
-            a2.in_count = c->w_cols.p;
-            a2.out_base = blocks;
-            a2.out_block_stride = b->block_stride;
-            a2.out_seg_stride = b->seg_stride;
-            a2.out_slots = c->w_oslots.p;
-            a2.out_slot_mode = OUT_SLOT_LIST;
-            a2.row_count = c->w_rows.p;
-            a2.slots_stride = c->k;
-            a2.coef = c->w_coef2.p;
-            a2.coef_block_stride = (uint64_t)dcs * dcs;
-            a2.coef_col_stride = dcs;
-            a2.vtab = c->d_vtab.p;
-            a2.nblocks = nb;
-            a2.vec_bytes = c->vec;
-            a2.accumulate = acc;
-            if ((rc = launch_gf8_matmul(a2, false, s))) return rc;
-        } else {
-            const uint32_t vb = c->vec & ~1u;
-            Gf16MatmulArgs a;
-            a.in_base = blocks;
-            a.in_block_stride = b->block_stride;
-            a.in_seg_stride = b->seg_stride;
-            a.in_slots = c->w_islots.p;
-            a.in_count = nd;
-            a.cols_const = c->k;
-            a.out_base = c->w_z.p;
-            a.out_block_stride = (uint64_t)dcs * zstride;
-            a.out_seg_stride = zstride;
-            a.out_slot_mode = OUT_SLOT_ROW;
-            a.row_count = t3dec ? c->w_rows1.p : c->w_rows.p;
-            a.slots_stride = c->k;
-            a.coef = reinterpret_cast<const uint16_t*>(c->w_coef1.p);
-            a.coef_block_stride = (uint64_t)c->k * dcs;
-            a.coef_col_stride = dcs;
-            a.exp_tab = reinterpret_cast<const uint16_t*>(c->d_exp.p);
-            a.log_tab = c->d_log.p;
-            a.nblocks = nb;
-            a.vec_bytes = vb;
-            if ((rc = launch_gf16_matmul(a, s))) return rc;
-            if (tw2) {
-                TwDecTablesArgs d;
-                d.coef2 = reinterpret_cast<const uint16_t*>(c->w_coef2.p);
-                d.dcs = dcs;
-                d.rows = c->w_rows.p;
-                d.out_slots = c->w_oslots.p;
-                d.slots_stride = c->k;
-                d.seg_stride = b->seg_stride;
-                d.nblocks = nb;
-                d.M = M2;
-                d.tw = c->w_tw2.p;
-                d.tw_block_stride = tw2_elems;
-                d.row_off = c->w_rowoff.p;
-                gf16_tw_field(d.phi, &d.lam);
-                if ((rc = launch_tw_dec_tables(d, s))) return rc;
-                Gf16T3Args t;
-                t.base = c->w_z.p;
-                t.block_stride = (uint64_t)dcs * zstride;
-                t.seg_stride = zstride;
-                t.nblocks = nb;
-                t.k = M2;
-                t.m = M2;
-                t.vec_bytes = vb;
-                t.tw = c->w_tw2.p;
-                t.tw_block_stride = tw2_elems;
-                t.blk_rows = c->w_rows.p;
-                t.row_off = c->w_rowoff.p;
-                t.row_off_stride = M2 + 12;
-                t.out_base = blocks;
-                t.out_block_stride = b->block_stride;
-                t.out_seg_stride = b->seg_stride;
-                rc = launch_gf16_tw_encode(t, s);
-                if (rc != NFEC_ENOTSUP) {
-                    if (rc) return rc;
-                    continue;
-                }
-            }
-            Gf16MatmulArgs a2 = a;
-            a2.in_base = c->w_z.p;
-            a2.in_block_stride = (uint64_t)dcs * zstride;
-            a2.in_seg_stride = zstride;
-            a2.in_slots = nullptr;
-            a2.in_count = c->w_cols.p;
-            a2.out_base = blocks;
-            a2.out_block_stride = b->block_stride;
-            a2.out_seg_stride = b->seg_stride;
-            a2.out_slots = c->w_oslots.p;
-            a2.out_slot_mode = OUT_SLOT_LIST;
-            a2.row_count = c->w_rows.p;
-            a2.coef = reinterpret_cast<const uint16_t*>(c->w_coef2.p);
-            a2.coef_block_stride = (uint64_t)dcs * dcs;
-            a2.accumulate = acc;
-            if ((rc = launch_gf16_matmul(a2, s))) return rc;
-        }
-    }
-    return NFEC_OK;
-}
-
-// counts each batch decode by the path that took it (nfec_codec_decode_paths)
-int decode_device(nfec_codec* c, const nfec_block_batch* b, const uint16_t* locs, uint32_t lstride,
-                  const uint16_t* counts, int32_t* status, hipStream_t s, bool caller_locked = false)
-{
-    int path = NFEC_DPATH_GENERIC;
-    bool tail = false;
-    const int rc = decode_device_impl(c, b, locs, lstride, counts, status, s, caller_locked, path, tail);
-    if (rc == NFEC_OK) c->dec_paths[path].fetch_add(1, std::memory_order_relaxed);
-    if (rc == NFEC_OK && tail) c->tail_batches[1].fetch_add(1, std::memory_order_relaxed);
-    return rc;
-}
-
-}  // namespace
+}  // namespace nfec
 
 // =====================================================================================
 // C ABI
@@ -2532,8 +771,8 @@ int nfec_decode_received(nfec_codec* codec, const nfec_block_batch* batch, const
     // launches, and reused by the next call in stream order, as the plan's buffers are
     std::lock_guard<std::mutex> lk(codec->mu);
     const uint32_t lstride = std::max(codec->m, 1u);
-    if ((rc = codec->w_rxlocs.reserve((size_t)batch->nblocks * lstride))) return rc;
-    if ((rc = codec->w_rxcounts.reserve(batch->nblocks))) return rc;
+    if ((rc = codec->ws.rxlocs.reserve((size_t)batch->nblocks * lstride))) return rc;
+    if ((rc = codec->ws.rxcounts.reserve(batch->nblocks))) return rc;
     RxErasureArgs a;
     a.received = received;
     a.mask_stride = mask_stride;
@@ -2541,11 +780,11 @@ int nfec_decode_received(nfec_codec* codec, const nfec_block_batch* batch, const
     a.k = codec->k;
     a.m = codec->m;
     a.nblocks = batch->nblocks;
-    a.locs = codec->w_rxlocs.p;
+    a.locs = codec->ws.rxlocs.p;
     a.stride = lstride;
-    a.counts = codec->w_rxcounts.p;
+    a.counts = codec->ws.rxcounts.p;
     if ((rc = launch_rx_erasures(a, s))) return rc;
-    return decode_device(codec, batch, codec->w_rxlocs.p, lstride, codec->w_rxcounts.p, status, s, true);
+    return decode_device(codec, batch, codec->ws.rxlocs.p, lstride, codec->ws.rxcounts.p, status, s, true);
 }
 
 // ---- per-call NORM semantics (synchronous, host vectors) ----

@@ -1,0 +1,130 @@
+#!/usr/bin/env python3
+"""Which kernels a device call launches: a fixed list of small encode / decode batches, one named
+case per invocation, to compare two builds of the library launch for launch.
+
+    python3 tools/dispatch_trace.py --list
+    rocprofv3 --kernel-trace --output-format csv -d DIR -o NAME -- \
+        python3 tools/dispatch_trace.py run CASE > counters.json
+    python3 tools/dispatch_trace.py join counters.json DIR     # one JSON line on stdout
+
+`run` makes the codec, runs the case's call once on 9 blocks (rs_plan2_kernel's four-block
+workgroups get a ragged last one) and prints the codec's path and tail counters.  `join` adds
+the ordered (kernel name, grid size, workgroup size, LDS bytes) of every library kernel in the
+trace.  NFEC_LIBRARY selects the build, as everywhere.  The path counters alone are too coarse:
+"fixed" does not say whether the fused kernels or the unfused stages ran.
+"""
+import csv
+import glob
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+NB = 9
+SHARED = 1  # NFEC_OPT_RS16_SHARED_TABLES
+
+# name: (call, kind, k, m, vec, keyword options)
+#   erase: "src16" 16 random source slots per block, "src+par" the same plus parity rows 0-15,
+#          N that many random slots of the whole block
+CASES = {
+    "dec_rs8_64_32_v1400_fdec3": ("dec", "RS8", 64, 32, 1400, {}),
+    "dec_rs8_64_32_v2048_fdec": ("dec", "RS8", 64, 32, 2048, {}),
+    "dec_rs8_64_8": ("dec", "RS8", 64, 8, 1400, {"erase": 8}),
+    "dec_rs8_64_32_parity_lost": ("dec", "RS8", 64, 32, 1400, {"erase": "src+par"}),
+    "dec_rs8_64_32_v1397_tail": ("dec", "RS8", 64, 32, 1397, {}),
+    "dec_rs8_64_32_shortened": ("dec", "RS8", 64, 32, 1400, {"short": True}),
+    "dec_rs8_64_32_accumulate": ("dec", "RS8", 64, 32, 1400, {"acc": True}),
+    "dec_rs8_20_10_v1000_rt": ("dec", "RS8", 20, 10, 1000, {"erase": 10}),
+    "dec_rs8_20_10_v1003_rt_tail": ("dec", "RS8", 20, 10, 1003, {"erase": 10}),
+    "dec_rs8_128_32": ("dec", "RS8", 128, 32, 1400, {"erase": 32}),
+    "dec_mdp_64_32_v1400": ("dec", "MDP", 64, 32, 1400, {}),
+    "dec_mdp_64_32_v1397": ("dec", "MDP", 64, 32, 1397, {}),
+    "dec_rs16_32_8_v64_tower": ("dec", "RS16", 32, 8, 64, {"erase": 8}),
+    "dec_rs16_32_8_shared_t3": ("dec", "RS16", 32, 8, 64, {"erase": 8, "opts": SHARED}),
+    "dec_rs16_160_80_shared_big_plan": ("dec", "RS16", 160, 80, 64, {"erase": 80, "opts": SHARED}),
+    # the smallest batch sub_batch splits: one block past the 65,536-block pass limit (38 MB)
+    "dec_rs8_64_8_two_passes": ("dec", "RS8", 64, 8, 8, {"erase": 8, "nb": 65537}),
+    "enc_rs8_64_32_v1400_d2": ("enc", "RS8", 64, 32, 1400, {}),
+    "enc_rs8_64_32_shortened_q4": ("enc", "RS8", 64, 32, 1400, {"short": True}),
+    "enc_rs8_64_32_accumulate": ("enc", "RS8", 64, 32, 1400, {"acc": True}),
+    "enc_rs8_64_32_v1397_tail": ("enc", "RS8", 64, 32, 1397, {}),
+    "enc_rs8_64_16": ("enc", "RS8", 64, 16, 1400, {}),
+    "enc_rs8_20_10": ("enc", "RS8", 20, 10, 1400, {}),
+    "enc_mdp_64_32": ("enc", "MDP", 64, 32, 1400, {}),
+    "enc_mdp_64_32_shortened": ("enc", "MDP", 64, 32, 1400, {"short": True}),
+    "enc_mdp_20_10": ("enc", "MDP", 20, 10, 1400, {}),
+    "enc_rs16_512_128_split": ("enc", "RS16", 512, 128, 64, {}),
+    "enc_rs16_32_8_shortened_tower": ("enc", "RS16", 32, 8, 64, {"short": True}),
+    "enc_rs16_32_8_shared": ("enc", "RS16", 32, 8, 64, {"opts": SHARED}),
+}
+
+
+def run(name):
+    import torch
+
+    import norm_amd.codec as C
+
+    call, kind, k, m, vec, kw = CASES[name]
+    nb, opts = kw.get("nb", NB), kw.get("opts", 0)
+    enc = getattr(C, "NormEncoder" + kind)(options=opts)
+    assert enc.Init(k, m, vec)
+    blocks = C.BlockLayout(k, m, vec).empty(nb)
+    nd = None
+    if kw.get("short"):
+        nd = torch.tensor([k - (i % 3) for i in range(nb)], dtype=torch.int16, device="cuda")
+    C.fill_blocks(blocks, k, vec, 7, per_block_num_data=nd)
+    codec = enc
+    if call == "enc":
+        enc.encode_blocks(blocks, num_data=nd, accumulate=kw.get("acc", False))
+    else:
+        enc.encode_blocks(blocks, num_data=nd)
+        codec = getattr(C, "NormDecoder" + kind)(options=opts)
+        assert codec.Init(k, m, vec)
+        erase = kw.get("erase", "src16")
+        if isinstance(erase, int):
+            rng = k - 2 + m if nd is not None else k + m
+            locs, counts = C.make_erasures(nb, rng, erase, 11, m)
+        else:
+            g = torch.Generator().manual_seed(11)
+            rows = []
+            for _ in range(nb):
+                src = sorted(torch.randperm(k - 2, generator=g)[:16].tolist())
+                rows.append(src + (list(range(k, k + 16)) if erase == "src+par" else []))
+            locs = torch.zeros((nb, m), dtype=torch.int16)
+            locs[:, : len(rows[0])] = torch.tensor(rows, dtype=torch.int16)
+            locs = locs.cuda()
+            counts = torch.full((nb,), len(rows[0]), dtype=torch.int16, device="cuda")
+        if not kw.get("acc"):
+            C.zero_erasures(blocks, locs, counts, vec)
+        codec.decode_blocks(blocks, locs, counts, num_data=nd, accumulate=kw.get("acc", False))
+    torch.cuda.synchronize()
+    print(json.dumps({"case": name, "encode_paths": enc.encode_paths(),
+                      "decode_paths": codec.decode_paths() if call == "dec" else None,
+                      "tail_batches": codec.tail_batches()}))
+
+
+def join(counters, trace_dir):
+    out = json.loads(open(counters).read().strip().splitlines()[-1])
+    files = glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True)
+    rows = [r for f in files for r in csv.DictReader(open(f))]
+    rows.sort(key=lambda r: int(r["Dispatch_Id"]))  # submission order (two streams may overlap in time)
+
+    def dims(r, stem):
+        return [int(r[f"{stem}_{a}"]) for a in "XYZ" if f"{stem}_{a}" in r] or [int(r[stem])]
+
+    out["kernels"] = [[r["Kernel_Name"].replace("nfec::(anonymous namespace)::", "").split("(")[0],
+                       dims(r, "Grid_Size"), dims(r, "Workgroup_Size"), int(r["LDS_Block_Size"])]
+                      for r in rows if "nfec" in r["Kernel_Name"]]
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    if sys.argv[1:] == ["--list"]:
+        print("\n".join(CASES))
+    elif len(sys.argv) == 3 and sys.argv[1] == "run" and sys.argv[2] in CASES:
+        run(sys.argv[2])
+    elif len(sys.argv) == 4 and sys.argv[1] == "join":
+        join(sys.argv[2], sys.argv[3])
+    else:
+        sys.exit(__doc__)

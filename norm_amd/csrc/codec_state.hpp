@@ -1,6 +1,7 @@
 // codec_state.hpp -- the codec object and what the translation units of the C ABI share:
-// nfec_api.cpp (construction, per-call and host paths, the ABI), dispatch_encode.cpp and
-// dispatch_decode.cpp (the device-batch dispatchers).  Internal; not installed.
+// nfec_api.cpp (construction, the device and receiver entries, the per-call paths, the host-only
+// repair, the utilities), dispatch_encode.cpp and dispatch_decode.cpp (the device-batch
+// dispatchers), host_pipeline.cpp (the host-resident batches).  Internal; not installed.
 #pragma once
 
 #include <algorithm>
@@ -84,7 +85,7 @@ struct HostSlot {
     uint8_t* pin = nullptr;     // pinned staging (pageable callers, segment lists)
     uint8_t* pin_dev = nullptr; // the same staging as the device addresses it (zero-copy kernels)
     uint16_t* dmeta = nullptr;  // num_data, erasure locs, counts
-    uint8_t* hmeta = nullptr;   // pinned mirror of dmeta (meta_up)
+    uint8_t* hmeta = nullptr;   // pinned mirror of dmeta (ChunkMeta)
     int32_t* dstat = nullptr;
     int32_t* hstat = nullptr;   // pinned status readback
     hipStream_t st = nullptr;
@@ -92,7 +93,8 @@ struct HostSlot {
     size_t dev_bytes = 0, pin_bytes = 0, meta_bytes = 0, dstat_bytes = 0, hstat_bytes = 0, hmeta_bytes = 0;
 };
 
-// host-batch pipeline resources cached per codec (run_host_batch / run_host_vectors)
+// host-batch pipeline resources cached per codec (host_pipeline.cpp: run_chunks claims the slots,
+// under nfec_codec::stage_mu)
 struct HostStage {
     HostSlot slot[kHostSlots];
     hipStream_t cst = nullptr;  // decode compute stream
@@ -303,6 +305,10 @@ struct nfec_codec {
 namespace nfec {
 
 // ---- shared between the translation units ----
+// the codec that runs per-call work and answers shape queries
+inline const nfec_codec* primary(const nfec_codec* c) { return c->stripes.empty() ? c : c->stripes[0].get(); }
+inline nfec_codec* primary(nfec_codec* c) { return c->stripes.empty() ? c : c->stripes[0].get(); }
+int host_only_fail();  // NFEC_EDEVICE: the codec was created with NFEC_OPT_HOST_ONLY
 int check_batch(const nfec_codec* c, const nfec_block_batch* b);
 // knobs (diagnostic library; the product takes the defaults): NFEC_FORCE_GENERIC, NFEC_BS_FLAGS,
 // NFEC_Q4, NFEC_ASM, NFEC_GF16_T3, NFEC_RS16_TW (nfec_api.cpp)

@@ -5,7 +5,7 @@
 // (built once on the host, uploaded to HBM) and the per-value kernel tables.  Batched calls
 // only enqueue kernels on the caller's stream; no host<->device traffic on the hot path.
 // The codec object is in codec_state.hpp; which kernels a device batch reaches is decided in
-// dispatch_encode.cpp and dispatch_decode.cpp.
+// dispatch_encode.cpp and dispatch_decode.cpp; the host-resident batches are in host_pipeline.cpp.
 #include <algorithm>
 #include <condition_variable>
 #include <cstdio>
@@ -35,14 +35,14 @@ int upload(DevBuf<uint8_t>& d, const void* src, size_t bytes)
     return NFEC_OK;
 }
 
+}  // namespace
+
+namespace nfec {
+
 int host_only_fail()
 {
     return fail(NFEC_EDEVICE, "host-only codec (NFEC_OPT_HOST_ONLY): no GPU path");
 }
-
-}  // namespace
-
-namespace nfec {
 
 int check_batch(const nfec_codec* c, const nfec_block_batch* b)
 {
@@ -471,10 +471,6 @@ int create_one(int device, int kind, uint32_t num_data, uint32_t num_parity, uin
     *out = c.release();
     return NFEC_OK;
 }
-
-// the codec that runs per-call work and answers shape queries
-const nfec_codec* primary(const nfec_codec* c) { return c->stripes.empty() ? c : c->stripes[0].get(); }
-nfec_codec* primary(nfec_codec* c) { return c->stripes.empty() ? c : c->stripes[0].get(); }
 
 // the stripe whose device holds a device batch (a single-device codec: itself).  Only device
 // allocations name a device: a batch in host-mapped or registered host memory (which the GPU
@@ -942,10 +938,6 @@ int nfec_encode_segment_host(nfec_codec* c, uint32_t segment_id, const void* dat
     return NFEC_OK;
 }
 
-namespace {
-unsigned host_copy_threads();
-}
-
 // The host repair's products: dst[r] (^)= sum_j coef[r][j] * srcs[j] over nelem bytes (GF(2^8))
 // or symbols (GF(2^16)), row dot products over pieces of the vectors, so a piece of every column
 // stays in cache while all rows take it; a repair of more than 8 MiB of products splits the
@@ -971,7 +963,7 @@ static int host_rows_apply(bool wide, void* const* dst, uint32_t nrows, const vo
         }
     };
     const unsigned nt = work > (8ull << 20)
-                            ? (unsigned)std::min<uint64_t>(std::min<uint64_t>(host_copy_threads(), work >> 22), nelem / 256)
+                            ? (unsigned)std::min<uint64_t>(std::min<uint64_t>(host_pool_size(), work >> 22), nelem / 256)
                             : 1u;
     if (nt <= 1) {
         run(0, nelem);
@@ -1229,873 +1221,6 @@ int nfec_decode_vectors(nfec_codec* c, void* const* vectors, uint32_t num_data, 
     return status;
 }
 
-// ---- host-resident batches: pinned staging, H2D || compute || D2H over two slots ----
-// Host-resident batches: a pipeline of device slots, each on its own stream, with the H2D
-// copy, the kernels and the D2H copy of chunk i overlapping chunk i+1's.  Only the bytes the
-// operation reads are uploaded and only the bytes it writes are downloaded:
-//   encode  (unshortened, overwrite): up source slots [0,k), down parity slots [k,k+m)
-//   encode  (shortened or accumulate): up/down the whole block span
-//   decode: up the whole block span, down source slots [0,k) (unerased bytes come back
-//           unchanged; parity slots are never written).
-// A pinned (page-locked / hipHostRegister'ed) caller buffer is DMA'd directly; a pageable one
-// goes through pinned staging with the copy split over host threads.
-namespace {
-
-bool host_is_pinned(const void* p)
-{
-    hipPointerAttribute_t at;
-    std::memset(&at, 0, sizeof(at));
-    const hipError_t e = hipPointerGetAttributes(&at, p);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return at.type == hipMemoryTypeHost;
-}
-
-// the device's address of pinned host memory (kernels read and write it over PCIe), or null
-uint8_t* host_device_ptr(const void* p)
-{
-    hipPointerAttribute_t at;
-    std::memset(&at, 0, sizeof(at));
-    if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeHost) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    return static_cast<uint8_t*>(at.devicePointer);
-}
-
-// pieces one host copy is cut into (at least 4 MiB each): as many as the process's host pool
-// has workers, which every concurrent call (and stripe) shares
-unsigned host_copy_threads() { return host_pool_size(); }
-
-// rows x width bytes, strided on both sides, split over host threads for large copies
-int copy2d(uint8_t* dst, uint64_t dpitch, const uint8_t* src, uint64_t spitch, uint64_t width, uint32_t rows)
-{
-    if (rows == 0 || width == 0) return NFEC_OK;
-    auto run = [=](uint32_t r0, uint32_t r1) {
-        if (dpitch == width && spitch == width) {
-            std::memcpy(dst + r0 * width, src + r0 * width, (size_t)(r1 - r0) * width);
-            return;
-        }
-        for (uint32_t r = r0; r < r1; ++r) std::memcpy(dst + r * dpitch, src + r * spitch, (size_t)width);
-    };
-    const uint64_t bytes = width * rows;
-    const unsigned nt = (unsigned)std::min<uint64_t>(std::min<uint64_t>(host_copy_threads(), rows),
-                                                      std::max<uint64_t>(1, bytes >> 22));
-    if (nt <= 1) {
-        run(0, rows);
-        return NFEC_OK;
-    }
-    const uint32_t per = (rows + nt - 1) / nt;
-    return host_parallel_for(nt, [&](unsigned t) {
-        const uint32_t r0 = std::min<uint32_t>(rows, t * per), r1 = std::min<uint32_t>(rows, r0 + per);
-        if (r0 < r1) run(r0, r1);
-    });
-}
-
-}  // namespace
-
-// ---- cached host staging ----
-// The pipelines' device slots, pinned staging, streams and events live in the codec and grow
-// on demand: allocating (and freeing, which synchronises the whole device) per call would
-// stall every other codec's work on the GPU -- two codecs driven from two host threads (the
-// mixed RS8/RS16 stream of BASELINE C5) would serialise.  Host-batch calls on one codec are
-// serialised by the codec's stage_mu (the reference's codec instances are single-threaded,
-// normApi.cpp:55,126; here concurrent callers of one codec wait rather than race).
-static int grow_dev(void** p, size_t& cap, size_t need)
-{
-    if (cap >= need) return NFEC_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    cap = 0;
-    if (hipMalloc(p, need) != hipSuccess) return fail(NFEC_ENOMEM, "staging allocation failed");
-    cap = need;
-    return NFEC_OK;
-}
-
-static int grow_pin(void** p, size_t& cap, size_t need)
-{
-    if (cap >= need) return NFEC_OK;
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr;
-    cap = 0;
-    if (hipHostMalloc(p, need, hipHostMallocDefault) != hipSuccess) return fail(NFEC_ENOMEM, "pinned staging allocation failed");
-    cap = need;
-    return NFEC_OK;
-}
-
-static int stage_slot(nfec_codec* c, uint32_t i, size_t dev_bytes, size_t pin_bytes, size_t meta_bytes,
-                      size_t stat_bytes, HostSlot*& out)
-{
-    HostSlot& s = c->stage.slot[i];
-    int rc;
-    const uint8_t* pin_before = s.pin;
-    if ((rc = grow_dev(reinterpret_cast<void**>(&s.dev), s.dev_bytes, dev_bytes)) ||
-        (pin_bytes && (rc = grow_pin(reinterpret_cast<void**>(&s.pin), s.pin_bytes, pin_bytes))) ||
-        (rc = grow_dev(reinterpret_cast<void**>(&s.dmeta), s.meta_bytes, meta_bytes)) ||
-        (rc = grow_pin(reinterpret_cast<void**>(&s.hmeta), s.hmeta_bytes, meta_bytes)) ||
-        (rc = grow_dev(reinterpret_cast<void**>(&s.dstat), s.dstat_bytes, stat_bytes)) ||
-        (rc = grow_pin(reinterpret_cast<void**>(&s.hstat), s.hstat_bytes, stat_bytes)))
-        return rc;
-    if (s.pin != pin_before) s.pin_dev = s.pin ? host_device_ptr(s.pin) : nullptr;
-    if (!s.st) {
-        const hipError_t se = hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking);
-        if (se != hipSuccess ||
-            hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&s.ev_up, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&s.ev_cd, hipEventDisableTiming) != hipSuccess)
-            return fail(NFEC_ENOMEM, "staging stream creation failed");
-    }
-    if (!c->stage.cst) {
-        // the decode kernels run at the highest stream priority: the slot moves of the other
-        // chunks are PCIe-bound and must not hold the CUs the compute waits for
-        int least = 0, greatest = 0;
-        if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) {
-            (void)hipGetLastError();
-            greatest = 0;
-        }
-        if (hipStreamCreateWithPriority(&c->stage.cst, hipStreamNonBlocking, greatest) != hipSuccess)
-            return fail(NFEC_ENOMEM, "staging stream creation failed");
-    }
-    out = &s;
-    return NFEC_OK;
-}
-
-// Per-chunk metadata (numData, erasure lists, counts) goes up through the slot's pinned mirror:
-// an async copy straight from the caller's pageable arrays is staged by the runtime and
-// blocks the host thread until the link drains, which stalls the pipeline behind the other
-// chunks' transfers.  (The slot is reused only after its previous chunk completed.)
-static hipError_t meta_up(HostSlot& s, uint16_t* dev, const uint16_t* src, size_t count)
-{
-    const size_t off = reinterpret_cast<uint8_t*>(dev) - reinterpret_cast<uint8_t*>(s.dmeta);
-    std::memcpy(s.hmeta + off, src, count * 2);
-    return hipMemcpyAsync(dev, s.hmeta + off, count * 2, hipMemcpyHostToDevice, s.st);
-}
-
-// Blocks per pipeline chunk: about 128 MiB (RS8(64,32) x 1400 B, 65,536 pinned blocks: 1,024-block
-// chunks 22.98 GiB/s, 2,048 22.7, 4,096 22.55, 512 21.68 on one box), but never fewer than the blocks it takes to fill
-// the GPU when the kernels run one wave per block (RS16, MDP, the generic RS8 kernels: 16 waves
-// per CU, 4096 blocks), and at most 4 GiB per slot.
-static uint32_t host_chunk(const nfec_codec* c, uint64_t dbs, uint32_t nblocks)
-{
-    if (const char* e = std::getenv("NFEC_HOST_CHUNK_BLOCKS"))  // tests: force multi-chunk pipelines
-        if (std::atol(e) > 0) return (uint32_t)std::min<uint64_t>((uint64_t)std::atol(e), nblocks);
-    const bool per_block = !(c->kind == NFEC_RS8 && has_bitsliced(c->k, c->m));
-    uint64_t ch = std::max<uint64_t>(1, (128ull << 20) / std::max<uint64_t>(dbs, 1));
-    if (per_block) ch = std::max<uint64_t>(ch, 4096);
-    ch = std::min<uint64_t>(ch, std::max<uint64_t>(1, (4ull << 30) / std::max<uint64_t>(dbs, 1)));
-    return (uint32_t)std::min<uint64_t>(ch, nblocks);
-}
-
-static void stage_drain(nfec_codec* c)
-{
-    for (auto& s : c->stage.slot)
-        if (s.st) (void)hipStreamSynchronize(s.st);
-    if (c->stage.cst) (void)hipStreamSynchronize(c->stage.cst);
-}
-
-// The codec's decode workspace (plan, z rows, inverses) is shared by all of its decode calls,
-// so the host pipelines run every chunk's decode on one compute stream: slot stream upload ->
-// event -> compute-stream decode -> event -> slot stream download.  (Encode reads only the
-// codec's constants and runs on the slot streams.)
-// Blocks whose numData (known on the host) equals k go to the unshortened fast kernels in
-// sub-batches of their own; only the others carry their numData.  NORM batches are mostly full
-// blocks with one short block ending each object, and one short block would otherwise send the
-// whole batch down the generic (numData-aware) kernels.  Full runs shorter than kMinFullRun stay
-// with their neighbours: a launch per handful of blocks costs more than it saves.
-extern "C++" template <typename F>
-static int split_full_runs(const uint16_t* hnd, uint32_t n, uint32_t k, F launch)
-{
-    constexpr uint32_t kMinFullRun = 32;
-    if (!hnd) return launch(0u, n, false);
-    uint32_t i = 0;
-    while (i < n) {
-        uint32_t rs = n, re = n;
-        for (uint32_t j = i; j < n;) {
-            if (hnd[j] != k) {
-                ++j;
-                continue;
-            }
-            uint32_t e = j;
-            while (e < n && hnd[e] == k) ++e;
-            if (e - j >= kMinFullRun) {
-                rs = j;
-                re = e;
-                break;
-            }
-            j = e;
-        }
-        int rc;
-        if (rs > i && (rc = launch(i, rs - i, true))) return rc;
-        if (rs < n && (rc = launch(rs, re - rs, false))) return rc;
-        i = re;
-    }
-    return NFEC_OK;
-}
-
-static int decode_serialized(nfec_codec* c, const nfec_block_batch* db, const uint16_t* dl, uint32_t lstride,
-                             const uint16_t* dc, HostSlot& s, uint32_t status_off = 0)
-{
-    NFEC_HIP(hipEventRecord(s.ev_up, s.st));
-    NFEC_HIP(hipStreamWaitEvent(c->stage.cst, s.ev_up, 0));
-    const int rc = decode_device(c, db, dl, lstride, dc, s.dstat + status_off, c->stage.cst);
-    if (rc) return rc;
-    NFEC_HIP(hipEventRecord(s.ev_cd, c->stage.cst));
-    NFEC_HIP(hipStreamWaitEvent(s.st, s.ev_cd, 0));
-    return NFEC_OK;
-}
-
-// One chunk of a host-resident decode with zero-copy slot moves (run_host_batch): metadata up
-// by DMA, the read slots gathered from host memory by a kernel (hdev: the caller's pinned
-// blocks as the device addresses them; null: a pageable caller, whose chunk is first copied
-// into the slot's pinned staging by host threads), the decode on the compute stream, the
-// repaired slots scattered back by a kernel, the status by DMA.  Ends with s.done recorded.
-static int host_decode_zc(nfec_codec* c, const nfec_block_batch* hb, HostSlot& s, uint32_t b0, uint32_t nb,
-                          uint32_t chunk, const uint16_t* locs, uint32_t lstride, const uint16_t* counts,
-                          uint8_t* hdev, uint64_t ul)
-{
-    const uint64_t hbs = hb->block_stride, ss = hb->seg_stride;
-    const uint64_t dbs = (uint64_t)(c->k + c->m) * ss;
-    uint8_t* hsrc = static_cast<uint8_t*>(hb->blocks) + (uint64_t)b0 * hbs;
-    uint16_t* dnd = hb->num_data ? s.dmeta : nullptr;
-    uint16_t* dlocs = s.dmeta + chunk;
-    uint16_t* dcnt = dlocs + (size_t)chunk * lstride;
-    hipError_t ae = meta_up(s, dlocs, locs + (uint64_t)b0 * lstride, (size_t)nb * lstride);
-    if (ae == hipSuccess) ae = meta_up(s, dcnt, counts + b0, nb);
-    if (ae == hipSuccess && dnd)
-        ae = meta_up(s, dnd, hb->num_data + b0, nb);
-    if (ae != hipSuccess) return hip_fail(ae, "host decode metadata upload");
-    SlotMoveArgs mv;
-    if (hdev) {
-        mv.src = hdev + (uint64_t)b0 * hbs;
-        mv.src_block_stride = hbs;
-    } else {
-        if (!s.pin_dev) return fail(NFEC_EDEVICE, "pinned staging is not device-mapped");
-        if (const int rc = copy2d(s.pin, dbs, hsrc, hbs, ul, nb)) return rc;
-        mv.src = s.pin_dev;
-        mv.src_block_stride = dbs;
-    }
-    mv.src_seg_stride = (uint32_t)ss;
-    mv.dst = s.dev;
-    mv.dst_block_stride = dbs;
-    mv.dst_seg_stride = (uint32_t)ss;
-    mv.nblocks = nb;
-    mv.k = c->k;
-    mv.m = c->m;
-    mv.bytes = c->vec;
-    mv.num_data = dnd;
-    mv.locs = dlocs;
-    mv.lstride = lstride;
-    mv.counts = dcnt;
-    mv.mode = c->kind == NFEC_MDP ? SLOTS_ALL_IN : SLOTS_RS_IN;
-    mv.accumulate = (hb->flags & NFEC_ACCUMULATE) ? 1u : 0u;
-    int rc = launch_slot_move(mv, s.st);
-    if (rc) return rc;
-    nfec_block_batch db = *hb;
-    db.blocks = s.dev;
-    db.block_stride = dbs;
-    db.nblocks = nb;
-    db.num_data = dnd;
-    // timing probes (diagnostic library): 1 no decode, 2 no scatter, 3 neither.  Measured (16k
-    // blocks RS8(64,32), tools/host_rate.py): 33.1 / 29.3 / 29.9 / 29.1 ms; a window DMA for the
-    // download instead of the scatter: 51 ms (DMA writes and zero-copy reads share the link badly)
-    static const long probe = diag_knob("NFEC_ZC_PROBE", 0, 0, 3);
-    if (!(probe & 1)) rc = split_full_runs(hb->num_data ? hb->num_data + b0 : nullptr, nb, c->k, [&](uint32_t o, uint32_t n, bool nd) {
-        nfec_block_batch sb = db;
-        sb.blocks = s.dev + o * dbs;
-        sb.nblocks = n;
-        sb.num_data = nd ? dnd + o : nullptr;
-        return decode_serialized(c, &sb, dlocs + (uint64_t)o * lstride, lstride, dcnt + o, s, o);
-    });
-    if (rc) return rc;
-    // repaired source slots back (RS16 never writes an odd last byte, normEncoderRS16.cpp:733)
-    SlotMoveArgs out = mv;
-    out.src = s.dev;
-    out.src_block_stride = dbs;
-    out.dst = hdev ? hdev + (uint64_t)b0 * hbs : s.pin_dev;
-    out.dst_block_stride = hdev ? hbs : dbs;
-    out.bytes = c->sym == 2 ? (c->vec & ~1u) : c->vec;
-    out.status = s.dstat;
-    out.mode = SLOTS_OUT;
-    if (!(probe & 2) && (rc = launch_slot_move(out, s.st))) return rc;
-    ae = hipMemcpyAsync(s.hstat, s.dstat, (size_t)nb * 4, hipMemcpyDeviceToHost, s.st);
-    if (ae == hipSuccess) ae = hipEventRecord(s.done, s.st);
-    return ae == hipSuccess ? NFEC_OK : hip_fail(ae, "host decode status");
-}
-
-// A host batch on a codec over several devices: contiguous block ranges [i*B/N, (i+1)*B/N), one
-// per stripe, each through that stripe's own pipeline on a host thread of its own (SURVEY 8e:
-// no exchange between the ranges).  fn(stripe, first block, blocks) runs one range.  The
-// first failing range's status and message are returned on the calling thread.
-extern "C++" template <typename F>
-static int run_striped(nfec_codec* c, uint32_t nblocks, F fn)
-{
-    const uint32_t ns = (uint32_t)std::min<size_t>(c->stripes.size(), std::max(nblocks, 1u));
-    std::vector<int> rcs(ns, NFEC_OK);
-    std::vector<std::string> errs(ns);
-    auto one = [&](uint32_t i) {
-        const uint32_t lo = (uint32_t)((uint64_t)nblocks * i / ns), hi = (uint32_t)((uint64_t)nblocks * (i + 1) / ns);
-        rcs[i] = hi > lo ? fn(c->stripes[i].get(), lo, hi - lo) : NFEC_OK;
-        if (rcs[i] < 0) errs[i] = last_error_cstr();
-    };
-    // one driver thread per stripe (they mostly wait on their GPU; the copies go to the host pool)
-    std::vector<std::thread> th;
-    std::vector<uint32_t> inline_ranges;
-    for (uint32_t i = 1; i < ns; ++i) {
-        try {
-            th.emplace_back(one, i);
-        } catch (...) {
-            inline_ranges.push_back(i);  // no thread to be had: that range on the calling thread
-        }
-    }
-    one(0);
-    for (uint32_t i : inline_ranges) one(i);
-    for (auto& t : th) t.join();
-    for (uint32_t i = 0; i < ns; ++i)
-        if (rcs[i] < 0) return fail(rcs[i], errs[i]);
-    return NFEC_OK;
-}
-
-static int run_host_batch(nfec_codec* c, const nfec_block_batch* hb, const uint16_t* locs, uint32_t lstride,
-                          const uint16_t* counts, int32_t* status, bool decode)
-{
-    int rc = check_batch(c, hb);
-    if (rc || hb->nblocks == 0) return rc;
-    if (!c->stripes.empty())
-        return run_striped(c, hb->nblocks, [&](nfec_codec* sc, uint32_t b0, uint32_t nb) {
-            nfec_block_batch sub = *hb;
-            sub.blocks = static_cast<uint8_t*>(hb->blocks) + (uint64_t)b0 * hb->block_stride;
-            sub.nblocks = nb;
-            sub.num_data = hb->num_data ? hb->num_data + b0 : nullptr;
-            return run_host_batch(sc, &sub, locs ? locs + (uint64_t)b0 * lstride : nullptr, lstride,
-                                  counts ? counts + b0 : nullptr, status ? status + b0 : nullptr, decode);
-        });
-    // numData is on the host here: reject what no block of k + m slots can hold before any
-    // transfer is sized from it (as run_host_vectors does)
-    if (hb->num_data)
-        for (uint32_t b = 0; b < hb->nblocks; ++b)
-            if (hb->num_data[b] == 0 || hb->num_data[b] > c->k) return fail(NFEC_EINVAL, "num_data out of range");
-    DeviceGuard g(c->device);
-    std::lock_guard<std::mutex> stage_lock(c->stage_mu);
-    const uint64_t hbs = hb->block_stride;
-    const uint64_t ss = hb->seg_stride;
-    const uint64_t dbs = (uint64_t)(c->k + c->m) * ss;       // compact device pitch
-    const uint64_t span = (uint64_t)(c->k + c->m - 1) * ss + c->vec;  // bytes a block op can touch
-    const bool acc = (hb->flags & NFEC_ACCUMULATE) != 0;
-    const bool partial_enc = !decode && !acc && !hb->num_data;
-    const uint64_t up_off = 0;
-    const uint64_t up_len = partial_enc ? (uint64_t)(c->k - 1) * ss + c->vec : span;
-    const uint64_t dn_off = partial_enc ? (uint64_t)c->k * ss : 0;
-    const uint64_t dn_len = partial_enc ? (uint64_t)(c->m - 1) * ss + c->vec
-                                        : (decode ? (uint64_t)(c->k - 1) * ss + c->vec : span);
-    // download pieces: parity slots one by one when slots carry padding (so the caller's
-    // bytes between vec and seg_stride are never overwritten)
-    std::vector<std::pair<uint64_t, uint64_t>> dn;
-    if (partial_enc && ss != c->vec)
-        for (uint32_t p = 0; p < c->m; ++p) dn.emplace_back((uint64_t)(c->k + p) * ss, (uint64_t)c->vec);
-    else
-        dn.emplace_back(dn_off, dn_len);
-    const bool pinned = host_is_pinned(hb->blocks);
-    uint8_t* const hbase = static_cast<uint8_t*>(hb->blocks);
-    // Decode moves its bytes by zero-copy kernels (launch_slot_move): up only the slots the
-    // decode reads (surviving source + the first e surviving parities; an erased source slot
-    // only when accumulating), down only the repaired source slots of blocks with status > 0.
-    // Per RS8(64,32) block with 16 source erasures that is 64 segments up and 16 down, against
-    // 80 and 64 for the window DMA below, which stays for encode and for device setups where
-    // the host memory is not mapped.
-    uint8_t* const hbase_dev = pinned ? host_device_ptr(hb->blocks) : nullptr;
-    const bool zc = decode && (pinned ? hbase_dev != nullptr : true) && (uint64_t)c->k + c->m <= 65536;
-    // RS decode reads the source slots and only the first e surviving parities of a block (P,
-    // normEncoderRS8.cpp:680-700), so a chunk's upload stops after the last parity slot any of
-    // its blocks uses: [0, k + 16) instead of the whole span for RS8(64,32) with 16 source
-    // erasures.  MDP decode reads every surviving vector (normEncoderMDP.cpp:346-361).
-    // The download then covers [0, max numData) of the chunk, which the upload always includes
-    // (slots past the upload hold another chunk's bytes and must not travel back).
-    auto decode_up_len = [&](uint32_t b0, uint32_t nb, uint64_t& down) -> uint64_t {
-        down = dn_len;
-        if (c->kind == NFEC_MDP) return span;
-        uint32_t top = 0, ndmax = 0;  // slots [0, top) are read by some block of the chunk
-        std::vector<uint8_t> erased(c->k + c->m);
-        for (uint32_t b = b0; b < b0 + nb; ++b) {
-            const uint32_t nd = hb->num_data ? hb->num_data[b] : c->k;
-            const uint32_t ec = std::min<uint32_t>(counts[b], lstride);
-            const uint16_t* l = locs + (uint64_t)b * lstride;
-            const uint32_t nvec = nd + c->m;
-            if (nd == 0 || nd > c->k) return span;
-            ndmax = std::max(ndmax, nd);
-            std::fill(erased.begin(), erased.begin() + nvec, 0);
-            uint32_t es = 0;
-            for (uint32_t i = 0; i < ec; ++i) {
-                if (l[i] >= nvec) return span;  // invalid list: the plan rejects it, stay safe
-                erased[l[i]] = 1;
-                es += l[i] < nd;
-            }
-            uint32_t used = 0, end = nd;
-            for (uint32_t v = nd; v < nvec && used < es; ++v)
-                if (!erased[v]) {
-                    ++used;
-                    end = v + 1;
-                }
-            if (used < es) return span;  // undecodable: nothing is read, but keep it simple
-            top = std::max(top, end);
-        }
-        down = (uint64_t)(ndmax - 1) * ss + c->vec;
-        return (uint64_t)(top - 1) * ss + c->vec;  // top >= ndmax >= 1
-    };
-
-    const uint32_t chunk = host_chunk(c, dbs, hb->nblocks);
-    const uint32_t used = std::min<uint32_t>(kHostSlots, (hb->nblocks + chunk - 1) / chunk);
-    const size_t meta = (size_t)chunk * (1 + lstride + 1);
-    HostSlot* sl[kHostSlots] = {};
-    for (uint32_t i = 0; i < used; ++i)
-        if ((rc = stage_slot(c, i, (size_t)chunk * dbs, pinned ? 0 : (size_t)chunk * dbs, meta * 2 + 16,
-                             (size_t)chunk * 4 + 16, sl[i])))
-            return rc;
-    struct Job {
-        uint32_t b0 = 0, nb = 0;
-        uint64_t dl = 0;  // decode: download length of the chunk's single piece
-        bool busy = false;
-    } jobs[kHostSlots];
-    auto finish = [&](uint32_t i) -> int {
-        Job& j = jobs[i];
-        HostSlot& s = *sl[i];
-        if (!j.busy) return NFEC_OK;
-        j.busy = false;
-        NFEC_HIP(hipEventSynchronize(s.done));
-        if (!pinned)
-            for (const auto& pc : dn)
-                if (const int rc = copy2d(hbase + (uint64_t)j.b0 * hbs + pc.first, hbs, s.pin + pc.first, dbs,
-                                          decode ? j.dl : pc.second, j.nb))
-                    return rc;
-        if (decode && status) std::memcpy(status + j.b0, s.hstat, (size_t)j.nb * 4);
-        return NFEC_OK;
-    };
-    auto bail = [&](int code) {
-        stage_drain(c);
-        return code;
-    };
-    uint32_t idx = 0;
-    for (uint32_t b0 = 0; b0 < hb->nblocks; b0 += chunk, ++idx) {
-        const uint32_t i = idx % used;
-        if ((rc = finish(i))) return bail(rc);
-        HostSlot& s = *sl[i];
-        Job& j = jobs[i];
-        j.b0 = b0;
-        j.nb = std::min(chunk, hb->nblocks - b0);
-        uint8_t* hsrc = hbase + (uint64_t)b0 * hbs;
-        uint64_t dl = dn_len;
-        const uint64_t ul = decode ? decode_up_len(b0, j.nb, dl) : up_len;
-        j.dl = dl;
-        hipError_t ae;
-        // (a pageable caller's chunk goes through the slot's pinned staging, which the zero-copy
-        // kernels need device-mapped; where it is not, the window DMA below takes the chunk)
-        if (zc && (pinned || s.pin_dev)) {
-            if ((rc = host_decode_zc(c, hb, s, b0, j.nb, chunk, locs, lstride, counts, pinned ? hbase_dev : nullptr,
-                                     ul)))
-                return bail(rc);
-            j.busy = true;
-            continue;
-        }
-        if (pinned) {
-            ae = hipMemcpy2DAsync(s.dev + up_off, dbs, hsrc + up_off, hbs, ul, j.nb, hipMemcpyHostToDevice, s.st);
-        } else {
-            if ((rc = copy2d(s.pin + up_off, dbs, hsrc + up_off, hbs, ul, j.nb))) return bail(rc);
-            ae = hipMemcpyAsync(s.dev, s.pin, (size_t)(j.nb - 1) * dbs + up_off + ul, hipMemcpyHostToDevice, s.st);
-        }
-        uint16_t* dnd = nullptr;
-        if (hb->num_data) {
-            dnd = s.dmeta;
-            if (ae == hipSuccess) ae = meta_up(s, dnd, hb->num_data + b0, j.nb);
-        }
-        nfec_block_batch db = *hb;
-        db.blocks = s.dev;
-        db.block_stride = dbs;
-        db.nblocks = j.nb;
-        db.num_data = dnd;
-        if (ae != hipSuccess) return bail(hip_fail(ae, "host batch upload"));
-        if (decode) {
-            uint16_t* dlocs = s.dmeta + chunk;
-            uint16_t* dcnt = dlocs + (size_t)chunk * lstride;
-            ae = meta_up(s, dlocs, locs + (uint64_t)b0 * lstride, j.nb * lstride);
-            if (ae == hipSuccess) ae = meta_up(s, dcnt, counts + b0, j.nb);
-            if (ae != hipSuccess) return bail(hip_fail(ae, "host batch upload"));
-            rc = split_full_runs(hb->num_data ? hb->num_data + b0 : nullptr, j.nb, c->k,
-                                 [&](uint32_t o, uint32_t n, bool nd) {
-                                     nfec_block_batch sb = db;
-                                     sb.blocks = s.dev + o * dbs;
-                                     sb.nblocks = n;
-                                     sb.num_data = nd ? dnd + o : nullptr;
-                                     return decode_serialized(c, &sb, dlocs + (uint64_t)o * lstride, lstride, dcnt + o, s, o);
-                                 });
-        } else {
-            rc = split_full_runs(hb->num_data ? hb->num_data + b0 : nullptr, j.nb, c->k,
-                                 [&](uint32_t o, uint32_t n, bool nd) {
-                                     nfec_block_batch sb = db;
-                                     sb.blocks = s.dev + o * dbs;
-                                     sb.nblocks = n;
-                                     sb.num_data = nd ? dnd + o : nullptr;
-                                     return encode_device(c, &sb, s.st);
-                                 });
-        }
-        if (rc) return bail(rc);
-        if (pinned)
-            for (size_t q = 0; q < dn.size() && ae == hipSuccess; ++q)
-                ae = hipMemcpy2DAsync(hsrc + dn[q].first, hbs, s.dev + dn[q].first, dbs, decode ? dl : dn[q].second,
-                                      j.nb, hipMemcpyDeviceToHost, s.st);
-        else
-            ae = hipMemcpyAsync(s.pin + dn_off, s.dev + dn_off, (size_t)(j.nb - 1) * dbs + (decode ? dl : dn_len),
-                                hipMemcpyDeviceToHost, s.st);
-        if (ae == hipSuccess && decode && status)
-            ae = hipMemcpyAsync(s.hstat, s.dstat, (size_t)j.nb * 4, hipMemcpyDeviceToHost, s.st);
-        if (ae == hipSuccess) ae = hipEventRecord(s.done, s.st);
-        if (ae != hipSuccess) return bail(hip_fail(ae, "host batch copy"));
-        j.busy = true;
-    }
-    for (uint32_t q = 0; q < used; ++q)
-        if ((rc = finish((idx + q) % used))) return bail(rc);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return bail(hip_fail(e, "host batch"));
-    return NFEC_OK;
-}
-
-// ---- host segment lists (NORM's scattered segment pool) ----
-// NormObject::CalculateBlockParity (src/common/normObject.cpp:2203-2229) and the receiver's
-// NormSenderNode::Decode path (normObject.cpp:1548-1644) hold a block as a list of segment
-// pointers from the segment pool (normSegment.cpp:14-86), not as one strided buffer.  These
-// batches gather the listed segments into pinned staging (host threads), run the device
-// kernels over a 3-slot H2D || compute || D2H pipeline, and scatter back only the bytes the
-// reference writes: parity slots for encode, the erased source slots for decode (RS16: the
-// even part of vector_size; an odd last byte is never written, normEncoderRS16.cpp:479).
-namespace {
-
-extern "C++" template <typename F>
-int parallel_blocks(uint32_t nb, uint64_t bytes, F fn)
-{
-    const unsigned nt = (unsigned)std::min<uint64_t>(std::min<uint64_t>(host_copy_threads(), nb),
-                                                      std::max<uint64_t>(1, bytes >> 22));
-    if (nt <= 1) {
-        fn(0u, nb);
-        return NFEC_OK;
-    }
-    const uint32_t per = (nb + nt - 1) / nt;
-    return host_parallel_for(nt, [&](unsigned t) {
-        const uint32_t b0 = std::min<uint32_t>(nb, t * per), b1 = std::min<uint32_t>(nb, b0 + per);
-        if (b0 < b1) fn(b0, b1);
-    });
-}
-
-// the segment-list gather of blocks [b0, b0 + nb): block b's slots [0, numData_b + extra) from
-// its pointer list (vecs[b * n + s]; NULL: zero) into dst + (b - b0) * dbs + s * ss, on the host
-// pool.  extra: m when the parity is read too (decode, accumulate), else 0.
-int gather_segments(uint8_t* dst, uint64_t dbs, uint64_t ss, void* const* vecs, uint32_t n, uint32_t b0, uint32_t nb,
-                     const uint16_t* num_data, uint32_t k, uint32_t extra, uint32_t vec)
-{
-    return parallel_blocks(nb, (uint64_t)nb * n * vec, [&](uint32_t i0, uint32_t i1) {
-        for (uint32_t i = i0; i < i1; ++i) {
-            const uint32_t b = b0 + i;
-            const uint32_t up = (num_data ? num_data[b] : k) + extra;
-            uint8_t* d = dst + (uint64_t)i * dbs;
-            for (uint32_t q = 0; q < up; ++q) {
-                const void* p = vecs[(uint64_t)b * n + q];
-                if (p) std::memcpy(d + q * ss, p, vec);
-                else std::memset(d + q * ss, 0, vec);
-            }
-        }
-    });
-}
-
-}  // namespace
-
-static int run_host_vectors(nfec_codec* c, void* const* vecs, uint32_t nblocks, const uint16_t* num_data,
-                            const uint16_t* locs, uint32_t lstride, const uint16_t* counts, int32_t* status,
-                            uint32_t flags, bool decode)
-{
-    if (!c || (nblocks && !vecs)) return fail(NFEC_EINVAL, "null codec or vector list");
-    if (primary(c)->host_only) return host_only_fail();
-    if (decode && (!locs || !counts || lstride == 0)) return fail(NFEC_EINVAL, "bad erasure arrays");
-    if (nblocks == 0) return NFEC_OK;
-    if (!c->stripes.empty())
-        return run_striped(c, nblocks, [&](nfec_codec* sc, uint32_t b0, uint32_t nb) {
-            return run_host_vectors(sc, vecs + (uint64_t)b0 * (c->k + c->m), nb, num_data ? num_data + b0 : nullptr,
-                                    locs ? locs + (uint64_t)b0 * lstride : nullptr, lstride,
-                                    counts ? counts + b0 : nullptr, status ? status + b0 : nullptr, flags, decode);
-        });
-    const uint32_t n = c->k + c->m;
-    const uint64_t ss = round_up(c->vec, 8u);
-    const uint64_t dbs = (uint64_t)n * ss;
-    const bool acc = (flags & NFEC_ACCUMULATE) != 0;
-    const size_t out_bytes = c->sym == 2 ? (c->vec & ~1u) : c->vec;
-    // validate the lists (the reference dereferences every source vector and, for encode,
-    // every parity vector; decode never touches missing parity, normEncoderRS8.cpp:689-711)
-    for (uint32_t b = 0; b < nblocks; ++b) {
-        const uint32_t nd = num_data ? num_data[b] : c->k;
-        if (nd == 0 || nd > c->k) return fail(NFEC_EINVAL, "num_data out of range");
-        const uint32_t need = decode ? nd : nd + c->m;
-        for (uint32_t s = 0; s < need; ++s)
-            if (!vecs[(uint64_t)b * n + s]) return fail(NFEC_EINVAL, "null source/parity vector");
-    }
-    DeviceGuard g(c->device);
-    std::lock_guard<std::mutex> stage_lock(c->stage_mu);
-    const uint32_t chunk = host_chunk(c, dbs, nblocks);
-    const uint32_t used = std::min<uint32_t>(kHostSlots, (nblocks + chunk - 1) / chunk);
-    const size_t meta = (size_t)chunk * (1 + lstride + 1);
-    HostSlot* sl[kHostSlots] = {};
-    int rc;
-    for (uint32_t i = 0; i < used; ++i)
-        if ((rc = stage_slot(c, i, (size_t)chunk * dbs, (size_t)chunk * dbs, meta * 2 + 16, (size_t)chunk * 4 + 16,
-                             sl[i])))
-            return rc;
-    struct Job {
-        uint32_t b0 = 0, nb = 0;
-        uint64_t dl = 0;  // decode: download length of the chunk's single piece
-        bool busy = false;
-    } jobs[kHostSlots];
-    auto gather = [&](HostSlot& s, const Job& j) {
-        // encode without accumulate reads the source only; everything else reads the whole
-        // listed block (absent parity is zero, as MDP's decoder treats it)
-        return gather_segments(s.pin, dbs, ss, vecs, n, j.b0, j.nb, num_data, c->k, (!decode && !acc) ? 0u : c->m,
-                               c->vec);
-    };
-    auto scatter = [&](HostSlot& s, const Job& j) {
-        return parallel_blocks(j.nb, (uint64_t)j.nb * (uint64_t)c->m * c->vec, [&](uint32_t i0, uint32_t i1) {
-            for (uint32_t i = i0; i < i1; ++i) {
-                const uint32_t b = j.b0 + i;
-                const uint32_t nd = num_data ? num_data[b] : c->k;
-                const uint8_t* src = s.pin + (uint64_t)i * dbs;
-                if (!decode) {
-                    for (uint32_t p = 0; p < c->m; ++p)
-                        std::memcpy(vecs[(uint64_t)b * n + nd + p], src + (nd + p) * ss, out_bytes);
-                } else if (s.hstat[i] > 0) {
-                    const uint16_t* l = locs + (uint64_t)b * lstride;
-                    for (uint32_t e = 0; e < counts[b] && e < lstride; ++e) {
-                        if (l[e] >= nd) break;  // only source erasures are filled (normEncoderRS8.cpp:732)
-                        std::memcpy(vecs[(uint64_t)b * n + l[e]], src + l[e] * ss, out_bytes);
-                    }
-                }
-            }
-        });
-    };
-    auto finish = [&](uint32_t i) -> int {
-        Job& j = jobs[i];
-        if (!j.busy) return NFEC_OK;
-        j.busy = false;
-        NFEC_HIP(hipEventSynchronize(sl[i]->done));
-        if (const int rc = scatter(*sl[i], j)) return rc;
-        if (decode && status) std::memcpy(status + j.b0, sl[i]->hstat, (size_t)j.nb * 4);
-        return NFEC_OK;
-    };
-    auto bail = [&](int code) {
-        stage_drain(c);
-        return code;
-    };
-    uint32_t idx = 0;
-    for (uint32_t b0 = 0; b0 < nblocks; b0 += chunk, ++idx) {
-        const uint32_t i = idx % used;
-        if ((rc = finish(i))) return bail(rc);
-        HostSlot& s = *sl[i];
-        Job& j = jobs[i];
-        j.b0 = b0;
-        j.nb = std::min(chunk, nblocks - b0);
-        if ((rc = gather(s, j))) return bail(rc);
-        // decode: the staged slots the decode reads go up by the zero-copy gather kernel (the
-        // erased source and unused parity stay on the host), the repaired ones come down by
-        // the scatter kernel (launch_slot_move, as in run_host_batch)
-        const bool zcv = decode && s.pin_dev && (uint64_t)n <= 65536;
-        hipError_t ae = zcv ? hipSuccess : hipMemcpyAsync(s.dev, s.pin, (size_t)j.nb * dbs, hipMemcpyHostToDevice, s.st);
-        uint16_t* dnd = nullptr;
-        if (num_data && ae == hipSuccess) {
-            dnd = s.dmeta;
-            ae = meta_up(s, dnd, num_data + b0, j.nb);
-        }
-        if (ae != hipSuccess) return bail(hip_fail(ae, "vector batch upload"));
-        nfec_block_batch db;
-        std::memset(&db, 0, sizeof(db));
-        db.blocks = s.dev;
-        db.block_stride = dbs;
-        db.seg_stride = (uint32_t)ss;
-        db.nblocks = j.nb;
-        db.num_data = dnd;
-        db.flags = flags;
-        if (decode) {
-            uint16_t* dl = s.dmeta + chunk;
-            uint16_t* dc = dl + (size_t)chunk * lstride;
-            ae = meta_up(s, dl, locs + (uint64_t)b0 * lstride, j.nb * lstride);
-            if (ae == hipSuccess) ae = meta_up(s, dc, counts + b0, j.nb);
-            if (ae != hipSuccess) return bail(hip_fail(ae, "vector batch upload"));
-            SlotMoveArgs mv;
-            if (zcv) {
-                mv.src = s.pin_dev;
-                mv.src_block_stride = dbs;
-                mv.src_seg_stride = (uint32_t)ss;
-                mv.dst = s.dev;
-                mv.dst_block_stride = dbs;
-                mv.dst_seg_stride = (uint32_t)ss;
-                mv.nblocks = j.nb;
-                mv.k = c->k;
-                mv.m = c->m;
-                mv.bytes = c->vec;
-                mv.num_data = dnd;
-                mv.locs = dl;
-                mv.lstride = lstride;
-                mv.counts = dc;
-                mv.mode = c->kind == NFEC_MDP ? SLOTS_ALL_IN : SLOTS_RS_IN;
-                mv.accumulate = acc ? 1u : 0u;
-                if ((rc = launch_slot_move(mv, s.st))) return bail(rc);
-            }
-            rc = split_full_runs(num_data ? num_data + b0 : nullptr, j.nb, c->k, [&](uint32_t o, uint32_t n, bool nd) {
-                nfec_block_batch sb = db;
-                sb.blocks = s.dev + o * dbs;
-                sb.nblocks = n;
-                sb.num_data = nd ? dnd + o : nullptr;
-                return decode_serialized(c, &sb, dl + (uint64_t)o * lstride, lstride, dc + o, s, o);
-            });
-            if (!rc && zcv) {
-                SlotMoveArgs out = mv;
-                out.src = s.dev;
-                out.dst = s.pin_dev;
-                out.bytes = (uint32_t)out_bytes;
-                out.status = s.dstat;
-                out.mode = SLOTS_OUT;
-                rc = launch_slot_move(out, s.st);
-            }
-            if (!rc) {
-                ae = hipMemcpyAsync(s.hstat, s.dstat, (size_t)j.nb * 4, hipMemcpyDeviceToHost, s.st);
-                if (ae != hipSuccess) return bail(hip_fail(ae, "vector batch status"));
-            }
-        } else {
-            rc = split_full_runs(num_data ? num_data + b0 : nullptr, j.nb, c->k, [&](uint32_t o, uint32_t n, bool nd) {
-                nfec_block_batch sb = db;
-                sb.blocks = s.dev + o * dbs;
-                sb.nblocks = n;
-                sb.num_data = nd ? dnd + o : nullptr;
-                return encode_device(c, &sb, s.st);
-            });
-        }
-        if (rc) return bail(rc);
-        // unshortened encode: only the parity region of each block comes back
-        if (zcv)
-            ae = hipSuccess;
-        else if (!decode && !num_data)
-            ae = hipMemcpy2DAsync(s.pin + (uint64_t)c->k * ss, dbs, s.dev + (uint64_t)c->k * ss, dbs, (uint64_t)c->m * ss,
-                                  j.nb, hipMemcpyDeviceToHost, s.st);
-        else
-            ae = hipMemcpyAsync(s.pin, s.dev, (size_t)j.nb * dbs, hipMemcpyDeviceToHost, s.st);
-        if (ae == hipSuccess) ae = hipEventRecord(s.done, s.st);
-        if (ae != hipSuccess) return bail(hip_fail(ae, "vector batch download"));
-        j.busy = true;
-    }
-    for (uint32_t q = 0; q < used; ++q)
-        if ((rc = finish((idx + q) % used))) return bail(rc);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return bail(hip_fail(e, "vector batch"));
-    return NFEC_OK;
-}
-
-int nfec_encode_host_vectors(nfec_codec* codec, void* const* vectors, uint32_t nblocks, const uint16_t* num_data,
-                             uint32_t flags)
-{
-    return run_host_vectors(codec, vectors, nblocks, num_data, nullptr, 0, nullptr, nullptr, flags, false);
-}
-
-int nfec_decode_host_vectors(nfec_codec* codec, void* const* vectors, uint32_t nblocks, const uint16_t* num_data,
-                             const uint16_t* erasure_locs, uint32_t erasure_stride, const uint16_t* erasure_counts,
-                             int32_t* status, uint32_t flags)
-{
-    return run_host_vectors(codec, vectors, nblocks, num_data, erasure_locs, erasure_stride, erasure_counts, status,
-                            flags, true);
-}
-
-int nfec_encode_host(nfec_codec* codec, const nfec_block_batch* host_batch)
-{
-    return run_host_batch(codec, host_batch, nullptr, 0, nullptr, nullptr, false);
-}
-
-int nfec_decode_host(nfec_codec* codec, const nfec_block_batch* host_batch, const uint16_t* erasure_locs,
-                     uint32_t erasure_stride, const uint16_t* erasure_counts, int32_t* status)
-{
-    if (!erasure_locs || !erasure_counts || erasure_stride == 0) return fail(NFEC_EINVAL, "bad erasure arrays");
-    return run_host_batch(codec, host_batch, erasure_locs, erasure_stride, erasure_counts, status, true);
-}
-
-// ---- asynchronous segment-list batches (receiver cross-block batching) ----
-// The receiver's decode site (NormObject::HandleObjectMessage -> NormSenderNode::Decode,
-// normObject.cpp:1548-1644, normNode.h:484-487) repairs one block per call on the protocol
-// thread.  These calls queue many blocks (from one remote sender's decoder) and return at
-// once; the protocol thread keeps receiving and collects completions with nfec_request_test /
-// nfec_request_wait.  The pointer table, numData, erasure lists and counts are copied at
-// submission; the segment buffers and status array must stay valid until completion.
-namespace {
-
-int submit_vectors(nfec_codec* c, void* const* vecs, uint32_t nblocks, const uint16_t* num_data, const uint16_t* locs,
-                   uint32_t lstride, const uint16_t* counts, int32_t* status, uint32_t flags, bool decode,
-                   nfec_request** out)
-{
-    if (!out) return fail(NFEC_EINVAL, "null request pointer");
-    *out = nullptr;
-    if (!c || (nblocks && !vecs)) return fail(NFEC_EINVAL, "null codec or vector list");
-    if (primary(c)->host_only) return host_only_fail();
-    if (decode && (!locs || !counts || lstride == 0)) return fail(NFEC_EINVAL, "bad erasure arrays");
-    const uint64_t n = (uint64_t)c->k + c->m;
-    auto tab = std::make_shared<std::vector<void*>>(vecs, vecs + n * nblocks);
-    auto nd = std::make_shared<std::vector<uint16_t>>();
-    if (num_data) nd->assign(num_data, num_data + nblocks);
-    auto el = std::make_shared<std::vector<uint16_t>>();
-    auto ec = std::make_shared<std::vector<uint16_t>>();
-    if (decode) {
-        el->assign(locs, locs + (uint64_t)lstride * nblocks);
-        ec->assign(counts, counts + nblocks);
-    }
-    std::unique_ptr<nfec_request> r(new nfec_request);
-    r->run = [=]() {
-        return run_host_vectors(c, tab->data(), nblocks, num_data ? nd->data() : nullptr,
-                                decode ? el->data() : nullptr, lstride, decode ? ec->data() : nullptr, status,
-                                flags, decode);
-    };
-    c->async.submit(r.get());
-    *out = r.release();
-    return NFEC_OK;
-}
-
-}  // namespace
-
-int nfec_encode_host_vectors_async(nfec_codec* codec, void* const* vectors, uint32_t nblocks, const uint16_t* num_data,
-                                   uint32_t flags, nfec_request** request)
-{
-    return submit_vectors(codec, vectors, nblocks, num_data, nullptr, 0, nullptr, nullptr, flags, false, request);
-}
-
-int nfec_decode_host_vectors_async(nfec_codec* codec, void* const* vectors, uint32_t nblocks,
-                                   const uint16_t* num_data, const uint16_t* erasure_locs, uint32_t erasure_stride,
-                                   const uint16_t* erasure_counts, int32_t* status, uint32_t flags,
-                                   nfec_request** request)
-{
-    return submit_vectors(codec, vectors, nblocks, num_data, erasure_locs, erasure_stride, erasure_counts, status,
-                          flags, true, request);
-}
-
-int nfec_request_test(nfec_request* r)
-{
-    if (!r) return fail(NFEC_EINVAL, "null request");
-    std::lock_guard<std::mutex> lk(r->mu);
-    return r->done ? 1 : 0;
-}
-
-int nfec_request_wait(nfec_request* r)
-{
-    if (!r) return fail(NFEC_EINVAL, "null request");
-    int rc;
-    std::string err;
-    {
-        std::unique_lock<std::mutex> lk(r->mu);
-        r->cv.wait(lk, [&] { return r->done; });
-        rc = r->rc;
-        err.swap(r->err);
-    }
-    delete r;
-    return rc < 0 ? fail(rc, err) : rc;
-}
-
 // ---- synthetic workload utilities ----
 int nfec_util_fill(const nfec_block_batch* b, uint32_t num_data, uint32_t vector_size, uint64_t seed,
                    uint64_t first_block, void* stream)
@@ -2139,44 +1264,6 @@ int nfec_util_pool_check(uint32_t pieces, int mode)
         ran.fetch_add(1);
     });
     return rc ? rc : (int)ran.load();
-}
-
-int nfec_util_gather_probe(void* const* vectors, uint32_t nblocks, uint32_t slots, uint32_t vector_size,
-                           uint32_t nstripes, uint32_t reps, double* seconds, uint32_t* max_active)
-{
-    if (!vectors || !seconds || nblocks == 0 || slots == 0 || vector_size == 0 || nstripes == 0 || nstripes > 64 ||
-        reps == 0)
-        return fail(NFEC_EINVAL, "bad argument");
-    const uint64_t ss = round_up(vector_size, 8u), dbs = (uint64_t)slots * ss;
-    const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, (128ull << 20) / dbs);  // the pipelines' 128 MiB chunks
-    std::vector<std::unique_ptr<uint8_t, void (*)(void*)>> stage;
-    for (uint32_t i = 0; i < nstripes; ++i) {
-        const uint64_t nb = (uint64_t)nblocks * (i + 1) / nstripes - (uint64_t)nblocks * i / nstripes;
-        void* p = nullptr;
-        const size_t bytes = (size_t)std::max<uint64_t>(1, std::min<uint64_t>(nb, chunk)) * dbs;
-        if (posix_memalign(&p, 4096, bytes)) return fail(NFEC_ENOMEM, "probe staging");
-        std::memset(p, 0, bytes);  // touched before timing
-        stage.emplace_back(static_cast<uint8_t*>(p), std::free);
-    }
-    auto stripe = [&](uint32_t i) {
-        const uint32_t lo = (uint32_t)((uint64_t)nblocks * i / nstripes), hi = (uint32_t)((uint64_t)nblocks * (i + 1) / nstripes);
-        for (uint32_t b0 = lo; b0 < hi; b0 += chunk)
-            (void)gather_segments(stage[i].get(), dbs, ss, vectors, slots, b0, std::min(chunk, hi - b0), nullptr, slots,
-                                  0, vector_size);
-    };
-    auto pass = [&] {
-        std::vector<std::thread> th;
-        for (uint32_t i = 1; i < nstripes; ++i) th.emplace_back(stripe, i);
-        stripe(0);
-        for (auto& t : th) t.join();
-    };
-    pass();  // untimed: first touches of the pool, the table and the staging
-    if (max_active) host_pool_max_active(true);
-    const auto t0 = std::chrono::steady_clock::now();
-    for (uint32_t r = 0; r < reps; ++r) pass();
-    *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / reps;
-    if (max_active) *max_active = host_pool_max_active(false);
-    return NFEC_OK;
 }
 
 int nfec_util_stream_copy(void* dst, const void* src, uint64_t bytes, void* stream)

@@ -365,7 +365,7 @@ int run_devices(const int32_t* devices, uint32_t ndev, uint64_t nblocks, F worke
         return rc;
     }
     // each worker's error message is thread-local: keep it and set it again on the calling thread
-    // for the first failing worker (as nfec_api.cpp's run_striped does)
+    // for the first failing worker (as host_pipeline.cpp's run_striped does)
     std::vector<int> rcs(ndev, NFEC_OK);
     std::vector<std::string> errs(ndev);
     auto one = [&](uint32_t i) {

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Which kernels a device call launches: a fixed list of small encode / decode batches, one named
-case per invocation, to compare two builds of the library launch for launch.
+"""Which kernels a call launches: a fixed list of small encode / decode batches, one named case
+per invocation, to compare two builds of the library launch for launch.
 
     python3 tools/dispatch_trace.py --list
     rocprofv3 --kernel-trace --output-format csv -d DIR -o NAME -- \
@@ -12,6 +12,11 @@ workgroups get a ragged last one) and prints the codec's path and tail counters.
 the ordered (kernel name, grid size, workgroup size, LDS bytes) of every library kernel in the
 trace.  NFEC_LIBRARY selects the build, as everywhere.  The path counters alone are too coarse:
 "fixed" does not say whether the fused kernels or the unfused stages ran.
+
+The host_* cases run a host-resident batch (nfec_*_host, nfec_*_host_vectors) in pipeline chunks
+of 4 blocks: three chunks, one per slot, the last ragged; the 13-block case reuses a slot.
+Trace them with `--kernel-trace --memory-copy-trace --output-format csv json`: `join` then also
+gives the multiset of copies, [direction, bytes, how many] (the JSON output carries the sizes).
 """
 import csv
 import glob
@@ -57,7 +62,39 @@ CASES = {
     "enc_rs16_512_128_split": ("enc", "RS16", 512, 128, 64, {}),
     "enc_rs16_32_8_shortened_tower": ("enc", "RS16", 32, 8, 64, {"short": True}),
     "enc_rs16_32_8_shared": ("enc", "RS16", 32, 8, 64, {"opts": SHARED}),
+    # host: "pinned" / "pageable" strided blocks, "vectors" segment lists; stride: seg_stride
+    "host_enc_rs8_pinned": ("enc", "RS8", 64, 32, 1400, {"host": "pinned"}),
+    "host_enc_rs8_pageable": ("enc", "RS8", 64, 32, 1400, {"host": "pageable"}),
+    "host_dec_rs8_pinned": ("dec", "RS8", 64, 32, 1400, {"host": "pinned"}),
+    "host_dec_rs8_pageable": ("dec", "RS8", 64, 32, 1400, {"host": "pageable"}),
+    "host_enc_rs8_vectors": ("enc", "RS8", 64, 32, 1400, {"host": "vectors"}),
+    "host_dec_rs8_vectors": ("dec", "RS8", 64, 32, 1400, {"host": "vectors"}),
+    "host_dec_rs8_shortened_pinned": ("dec", "RS8", 64, 32, 1400, {"host": "pinned", "short": True}),
+    "host_dec_mdp_24_8_v600_pageable": ("dec", "MDP", 24, 8, 600, {"host": "pageable", "erase": 8}),
+    "host_enc_rs16_30_10_v998_pinned": ("enc", "RS16", 30, 10, 998, {"host": "pinned", "stride": 1000}),
+    "host_dec_rs8_13_blocks_pinned": ("dec", "RS8", 64, 32, 1400, {"host": "pinned", "nb": 13}),
 }
+
+
+def _host_call(codec, call, how, blocks, nd, acc, locs=None, counts=None):
+    """the case's call on a host copy of the device batch"""
+    import numpy as np
+    import torch
+
+    t = blocks.cpu()
+    arr = (t.pin_memory() if how == "pinned" else t).numpy()
+    hnd = None if nd is None else nd.cpu().numpy().view(np.uint16)
+    dec = () if call == "enc" else (locs.cpu().numpy().view(np.uint16), counts.cpu().numpy().view(np.uint16))
+    torch.cuda.synchronize()
+    os.environ["NFEC_HOST_CHUNK_BLOCKS"] = "4"
+    if how == "vectors":
+        segs = [[arr[b, s].copy() for s in range((codec.ndata if hnd is None else int(hnd[b])) + codec.npar)]
+                for b in range(arr.shape[0])]
+        fn = codec.encode_vectors_host if call == "enc" else codec.decode_vectors_host
+    else:
+        segs = arr
+        fn = codec.encode_blocks_host if call == "enc" else codec.decode_blocks_host
+    fn(segs, *dec, num_data=hnd, accumulate=acc)
 
 
 def run(name):
@@ -69,13 +106,16 @@ def run(name):
     nb, opts = kw.get("nb", NB), kw.get("opts", 0)
     enc = getattr(C, "NormEncoder" + kind)(options=opts)
     assert enc.Init(k, m, vec)
-    blocks = C.BlockLayout(k, m, vec).empty(nb)
+    blocks = C.BlockLayout(k, m, vec, kw.get("stride")).empty(nb)
+    how = kw.get("host")
     nd = None
     if kw.get("short"):
         nd = torch.tensor([k - (i % 3) for i in range(nb)], dtype=torch.int16, device="cuda")
     C.fill_blocks(blocks, k, vec, 7, per_block_num_data=nd)
     codec = enc
-    if call == "enc":
+    if call == "enc" and how:
+        _host_call(enc, call, how, blocks, nd, kw.get("acc", False))
+    elif call == "enc":
         enc.encode_blocks(blocks, num_data=nd, accumulate=kw.get("acc", False))
     else:
         enc.encode_blocks(blocks, num_data=nd)
@@ -97,7 +137,10 @@ def run(name):
             counts = torch.full((nb,), len(rows[0]), dtype=torch.int16, device="cuda")
         if not kw.get("acc"):
             C.zero_erasures(blocks, locs, counts, vec)
-        codec.decode_blocks(blocks, locs, counts, num_data=nd, accumulate=kw.get("acc", False))
+        if how:
+            _host_call(codec, call, how, blocks, nd, kw.get("acc", False), locs, counts)
+        else:
+            codec.decode_blocks(blocks, locs, counts, num_data=nd, accumulate=kw.get("acc", False))
     torch.cuda.synchronize()
     print(json.dumps({"case": name, "encode_paths": enc.encode_paths(),
                       "decode_paths": codec.decode_paths() if call == "dec" else None,
@@ -116,6 +159,19 @@ def join(counters, trace_dir):
     out["kernels"] = [[r["Kernel_Name"].replace("nfec::(anonymous namespace)::", "").split("(")[0],
                        dims(r, "Grid_Size"), dims(r, "Workgroup_Size"), int(r["LDS_Block_Size"])]
                       for r in rows if "nfec" in r["Kernel_Name"]]
+    copies = {}
+    for f in glob.glob(os.path.join(trace_dir, "**", "*results.json"), recursive=True):
+        for tool in json.load(open(f))["rocprofiler-sdk-tool"]:
+            names = []
+            for e in tool.get("strings", {}).get("buffer_records", []):
+                if e.get("kind") == "MEMORY_COPY":
+                    names = e.get("operations", [])
+            for r in tool.get("buffer_records", {}).get("memory_copy", []):
+                op = r["operation"]
+                key = (names[op] if isinstance(op, int) and op < len(names) else str(op), int(r["bytes"]))
+                copies[key] = copies.get(key, 0) + 1
+    if copies:
+        out["copies"] = [[d, b, n] for (d, b), n in sorted(copies.items())]
     print(json.dumps(out))
 
 

@@ -22,6 +22,12 @@
  *   nfec_decode           NormDecoder::Decode  (RS8 normEncoderRS8.cpp:652-757, RS16 :650-755,
  *                         MDP normEncoderMDP.cpp:333-430) for many blocks at once, as called
  *                         from NormObject::HandleObjectMessage src/common/normObject.cpp:1548-1644
+ *   nfec_rx_place / nfec_decode_received
+ *                         the segment copy, the reception mask and the erasure list of
+ *                         NormObject::HandleObjectMessage  src/common/normObject.cpp:1548-1644
+ *   nfec_tx_list / nfec_tx_emit
+ *                         the pending walk, the payload lengths, the FEC payload ID and UnsetPending
+ *                         of NormObject::NextSenderMsg  src/common/normObject.cpp:1877-2078
  *   nfec_encode_host_vectors / nfec_decode_host_vectors
  *                         the same two sites on NORM's scattered segment lists (block->SegmentList())
  *   nfec_encode_segment   NormEncoder::Encode(segmentId, dataVector, parityVectorList)
@@ -267,6 +273,79 @@ int nfec_decode_received(nfec_codec* codec, const nfec_block_batch* batch, const
 int nfec_rx_erasures_host(uint32_t k, uint32_t m, const uint32_t* received, uint32_t mask_stride,
                           const uint16_t* num_data, uint32_t nblocks, uint16_t* erasure_locs,
                           uint32_t erasure_stride, uint16_t* erasure_counts);
+
+/* ---- sender assembly on the device ----
+ * What NormObject::NextSenderMsg does once a block's parity exists (normObject.cpp:1877-2078) for
+ * a sender whose blocks are in HBM: walk the blocks and their pending masks in order, pick each
+ * segment's payload length, write the FEC payload ID in front of the payload and clear the
+ * pending bit.  The mirror of the receiver section: nfec_tx_list's four arrays are the ones
+ * nfec_rx_segments takes, so a loopback needs no conversion.  Device entries are asynchronous on
+ * stream; nfec_tx_list runs on the codec device that holds the mask, nfec_tx_emit on the one that
+ * holds the batch.  Neither owns codec state: calls may run concurrently with anything.
+ *
+ * A pending mask has the reception mask's layout: uint32_t pending[nblocks][mask_stride],
+ * mask_stride >= (k + m + 31) / 32, bit s % 32 of word s / 32 is slot s.  The caller sets it as
+ * NormBlock::TxInit does (normSegment.h:106-118: bits [0, numData + autoParity)) and as TxUpdate /
+ * ActivateRepairs do (normSegment.cpp:261-339).  Bits at or past numData_b + m are ignored.
+ *
+ * The transmission list.  With nd_b = num_data ? num_data[b] : k (device [nblocks] or NULL), the
+ * entries are: blocks ascending, within a block the pending slots of [0, nd_b + m) ascending
+ * (NextSenderMsg's first-pending-block / first-pending-segment walk, :1877, :1989); a block whose
+ * nd_b is outside [1, k] lists nothing.  seg_length: device uint16 [nblocks][length_stride],
+ * length_stride >= k, or NULL.  A source slot s < nd_b is listed with length seg_length[b][s], a
+ * parity slot with the block's seg_size_max, the maximum of seg_length[b][0 .. nd_b) over all
+ * source slots, pending or not (:2050, :2071); with seg_length NULL both are vector_size.  A
+ * length above vector_size is listed as it is (nfec_tx_emit rejects it).  Offsets are packed
+ * behind `gap` free bytes per message (room for the message header and the payload ID): entry i's
+ * payload starts at (i + 1) * gap + the lengths of the entries before it.
+ * block_start: device uint64 [nblocks + 1][2]; block_start[b] = {index of block b's first entry,
+ * byte offset at which its first message's gap begins}, row nblocks = the totals {entries, bytes}.
+ * The totals are the full numbers even past capacity; only the first `capacity` entries of the
+ * four arrays are written (nfec_rx_erasures' rule for erasure_stride).  block_start is also the
+ * call's only workspace. */
+int nfec_tx_list(const nfec_codec* codec, const uint32_t* pending, uint32_t mask_stride,
+                 const uint16_t* num_data, uint32_t nblocks, const uint16_t* seg_length,
+                 uint32_t length_stride, uint32_t gap, uint64_t* offsets, uint32_t* block_index,
+                 uint16_t* symbol_id, uint16_t* length, uint32_t capacity, uint64_t* block_start,
+                 void* stream);
+/* nfec_tx_list's rule on host arrays: no codec, no GPU.  NFEC_EINVAL for null arrays, k or m of 0,
+ * k + m > 65536, a vector_size outside [1, 65535], a mask_stride below (k + m + 31) / 32 or a
+ * length_stride below k. */
+int nfec_tx_list_host(uint32_t k, uint32_t m, uint32_t vector_size, const uint32_t* pending,
+                      uint32_t mask_stride, const uint16_t* num_data, uint32_t nblocks,
+                      const uint16_t* seg_length, uint32_t length_stride, uint32_t gap,
+                      uint64_t* offsets, uint32_t* block_index, uint16_t* symbol_id, uint16_t* length,
+                      uint32_t capacity, uint64_t* block_start);
+
+typedef struct nfec_tx_segments {      /* device arrays, as nfec_tx_list writes them */
+    void* payloads;                    /* the wire buffer, any byte alignment           */
+    uint64_t payload_bytes;            /* ... and its size                              */
+    const uint64_t* offsets;           /* [count]: byte offset of entry i's payload     */
+    const uint32_t* block_index;       /* [count]: block of the batch                   */
+    const uint16_t* symbol_id;         /* [count]: slot                                 */
+    const uint16_t* length;            /* [count]: payload bytes, <= vector_size        */
+    uint32_t count;                    /* entries the arrays hold (upper bound)         */
+    const uint64_t* count_dev;         /* device, may be NULL: process min(count, *count_dev)
+                                          entries (block_start's total), so list -> emit
+                                          chains on a stream without a synchronize       */
+} nfec_tx_segments;
+
+/* Entry i, with b = block_index[i], s = symbol_id[i], len = length[i], off = offsets[i] and idlen =
+ * nfec_payload_id_length(fec_id) (0 for fec_id 0: no payload ID), writes the bytes [off - idlen,
+ * off + len) of payloads: first what nfec_payload_id_write(fec_id, fec_m, first_block_id + b
+ * (32-bit wrap), s, nd_b, ...) writes, then the first len bytes of slot s of block b.  No other
+ * byte of payloads is written, or read and written back: the neighbouring message may share a
+ * cache line.  No byte outside the slot's own seg_stride bytes is read.  With pending given (may
+ * be NULL) the slot's bit is cleared by one atomic AND (UnsetPending, normObject.cpp:2075).
+ * An entry is rejected, with no byte and no mask word written, when b >= nblocks, nd_b is outside
+ * [1, k], s >= nd_b + m, len > vector_size, off < idlen or off + len > payload_bytes: a wrong
+ * descriptor cannot make the call write outside the wire buffer or read outside the batch.
+ * stats (device [2], may be NULL; the caller zeroes it): the emitted and rejected counts are
+ * added to stats[0..1].  NFEC_EINVAL for a fec_id / fec_m pair nfec_payload_id_write refuses.
+ * batch->flags is ignored; the batch is only read. */
+int nfec_tx_emit(const nfec_codec* codec, const nfec_block_batch* batch, const nfec_tx_segments* segments,
+                 uint8_t fec_id, uint8_t fec_m, uint32_t first_block_id, uint32_t* pending,
+                 uint32_t mask_stride, uint32_t* stats, void* stream);
 
 /* ---- host-resident batched path: same layouts, host pointers (pageable or pinned).
  * Staged through pinned buffers with H2D / compute / D2H overlapped on streams.

@@ -60,6 +60,20 @@ class RxSegments(ctypes.Structure):
     ]
 
 
+class TxSegments(ctypes.Structure):
+    """nfec_tx_segments: the wire buffer and the transmission list (device arrays)."""
+    _fields_ = [
+        ("payloads", ctypes.c_void_p),
+        ("payload_bytes", ctypes.c_uint64),
+        ("offsets", ctypes.c_void_p),
+        ("block_index", ctypes.c_void_p),
+        ("symbol_id", ctypes.c_void_p),
+        ("length", ctypes.c_void_p),
+        ("count", ctypes.c_uint32),
+        ("count_dev", ctypes.c_void_p),
+    ]
+
+
 class CodecInfo(ctypes.Structure):
     _fields_ = [
         ("kind", ctypes.c_int32),
@@ -154,6 +168,10 @@ _SIGS = {
     "nfec_rx_erasures": (_I, [_P, _P, _U32, _P, _U32, _P, _U32, _P, _P]),
     "nfec_decode_received": (_I, [_P, ctypes.POINTER(BlockBatch), _P, _U32, _P, _P]),
     "nfec_rx_erasures_host": (_I, [_U32, _U32, _P, _U32, _P, _U32, _P, _U32, _P]),
+    "nfec_tx_list": (_I, [_P, _P, _U32, _P, _U32, _P, _U32, _U32, _P, _P, _P, _P, _U32, _P, _P]),
+    "nfec_tx_list_host": (_I, [_U32, _U32, _U32, _P, _U32, _P, _U32, _P, _U32, _U32, _P, _P, _P, _P, _U32, _P]),
+    "nfec_tx_emit": (_I, [_P, ctypes.POINTER(BlockBatch), ctypes.POINTER(TxSegments), _U8, _U8, _U32, _P, _U32, _P,
+                          _P]),
     "nfec_encode_host": (_I, [_P, ctypes.POINTER(BlockBatch)]),
     "nfec_decode_host": (_I, [_P, ctypes.POINTER(BlockBatch), _P, _U32, _P, _P]),
     "nfec_encode_host_vectors": (_I, [_P, _P, _U32, _P, _U32]),

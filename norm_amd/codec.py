@@ -253,6 +253,77 @@ class _Codec:
                                          _tensor_ptr(counts, "counts"), _stream_handle(stream)), "nfec_rx_erasures")
         return locs, counts
 
+    # -- sender assembly on the device (nfec.h, "sender assembly on the device") --
+    def list_pending(self, pending, num_data=None, seg_length=None, gap=0, capacity=None, stream=None):
+        """The transmission list of a pending mask (nfec_tx_list), in NextSenderMsg's order:
+        (offsets int64, block_index int32, symbol_id int16, length int16, block_start int64
+        [nblocks + 1, 2]).  pending: 32-bit tensor [nblocks, mask_stride]; seg_length: 16-bit
+        tensor [nblocks, >= k] of the source segments' lengths, or None (all vector_size); gap:
+        bytes left free in front of every payload.  The four arrays hold `capacity` entries
+        (default: every slot of every block); block_start[nblocks] = (entries, wire bytes) is the
+        full total even past capacity, and block_start[nblocks, :1] is emit_segments' count_dev."""
+        import torch
+
+        self._need()
+        _mask_check(pending, pending.shape[0])
+        nb = pending.shape[0]
+        capacity = nb * (self.ndata + self.npar) if capacity is None else capacity
+        lstride = 0
+        if seg_length is not None:
+            if seg_length.dim() != 2 or seg_length.element_size() != 2 or seg_length.shape[0] != nb:
+                raise ValueError("seg_length must be a 16-bit tensor [nblocks, length_stride]")
+            lstride = seg_length.shape[1]
+        dev = pending.device
+        offsets = torch.zeros(capacity, dtype=torch.int64, device=dev)
+        block_index = torch.zeros(capacity, dtype=torch.int32, device=dev)
+        symbol_id = torch.zeros(capacity, dtype=torch.int16, device=dev)
+        length = torch.zeros(capacity, dtype=torch.int16, device=dev)
+        block_start = torch.zeros((nb + 1, 2), dtype=torch.int64, device=dev)
+        N.check(N.lib().nfec_tx_list(self._h, _tensor_ptr(pending, "pending"), pending.shape[1],
+                                     _tensor_ptr(num_data, "num_data"), nb, _tensor_ptr(seg_length, "seg_length"),
+                                     lstride, gap, _tensor_ptr(offsets, "offsets"),
+                                     _tensor_ptr(block_index, "block_index"), _tensor_ptr(symbol_id, "symbol_id"),
+                                     _tensor_ptr(length, "length"), capacity, _tensor_ptr(block_start, "block_start"),
+                                     _stream_handle(stream)), "nfec_tx_list")
+        return offsets, block_index, symbol_id, length, block_start
+
+    def emit_segments(self, blocks, payloads, offsets, block_index, symbol_id, length, count_dev=None, fec_id=0,
+                      fec_m=8, first_block_id=0, pending=None, num_data=None, stats=None, stream=None):
+        """Write the listed slots of a device batch into the wire buffer `payloads` (uint8 tensor),
+        each behind its FEC payload ID (nfec_tx_emit; fec_id 0: no ID).  The four descriptor tensors
+        are list_pending's; count_dev: a one-element int64 CUDA tensor (block_start[nblocks, :1])
+        that bounds the entries processed, or None.  pending: the mask whose bits are cleared, or
+        None.  stats: int32 [2] the emitted and rejected counts are added to (zero it first), or
+        None."""
+        self._need()
+        b = _batch_struct(blocks, num_data, False)
+        if pending is not None:
+            _mask_check(pending, blocks.shape[0])
+        count = offsets.numel()
+        for t, size, what in ((offsets, 8, "offsets"), (block_index, 4, "block_index"), (symbol_id, 2, "symbol_id"),
+                              (length, 2, "length")):
+            if t.element_size() != size or t.numel() != count:
+                raise ValueError(f"{what} must hold {count} elements of {size} bytes")
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous CUDA (HIP) tensor")
+        if stats is not None and (stats.element_size() != 4 or stats.numel() < 2):
+            raise ValueError("stats must hold two 32-bit counters")
+        if count_dev is not None and (count_dev.element_size() != 8 or count_dev.numel() < 1 or not count_dev.is_cuda):
+            raise ValueError("count_dev must be a 64-bit CUDA (HIP) tensor")
+        if payloads.element_size() != 1 or not payloads.is_cuda or not payloads.is_contiguous():
+            raise ValueError("payloads must be a contiguous uint8 CUDA (HIP) tensor")
+        seg = N.TxSegments()
+        seg.payloads = payloads.data_ptr() if payloads.numel() else None
+        seg.payload_bytes = payloads.numel()
+        seg.offsets, seg.block_index = offsets.data_ptr(), block_index.data_ptr()
+        seg.symbol_id, seg.length = symbol_id.data_ptr(), length.data_ptr()
+        seg.count = count
+        seg.count_dev = count_dev.data_ptr() if count_dev is not None else None
+        N.check(N.lib().nfec_tx_emit(self._h, ctypes.byref(b), ctypes.byref(seg), fec_id, fec_m,
+                                     first_block_id & 0xFFFFFFFF, _tensor_ptr(pending, "pending"),
+                                     pending.shape[1] if pending is not None else 0, _tensor_ptr(stats, "stats"),
+                                     _stream_handle(stream)), "nfec_tx_emit")
+
     def _need(self):
         if not self._h:
             raise RuntimeError("codec not initialised (call Init)")
@@ -521,6 +592,39 @@ def erasures_from_received_host(k, m, received, num_data=None, stride=None):
     N.check(N.lib().nfec_rx_erasures_host(k, m, mask.ctypes.data, mask.shape[1], None if nd is None else nd.ctypes.data,
                                           nb, locs.ctypes.data, stride, counts.ctypes.data), "nfec_rx_erasures_host")
     return locs, counts
+
+
+def tx_list_host(k, m, vector_size, pending, num_data=None, seg_length=None, gap=0, capacity=None):
+    """nfec_tx_list_host: the transmission list of pending masks in host memory (no GPU).  pending:
+    NumPy 32-bit array [nblocks, mask_stride]; seg_length: 16-bit array [nblocks, >= k] or None.
+    Returns (offsets uint64, block_index uint32, symbol_id uint16, length uint16, block_start uint64
+    [nblocks + 1, 2]); the four arrays hold `capacity` entries (default nblocks * (k + m)) and stay
+    zero past the list's end."""
+    import numpy as np
+
+    mask = np.ascontiguousarray(pending).view(np.uint32)
+    if mask.ndim != 2:
+        raise ValueError("pending must be a 32-bit array [nblocks, mask_stride]")
+    nb = mask.shape[0]
+    capacity = nb * (k + m) if capacity is None else capacity
+    nd = None if num_data is None else np.ascontiguousarray(num_data, dtype=np.uint16)
+    lens, lstride = None, 0
+    if seg_length is not None:
+        lens = np.ascontiguousarray(seg_length).view(np.uint16)
+        if lens.ndim != 2 or lens.shape[0] != nb:
+            raise ValueError("seg_length must be a 16-bit array [nblocks, length_stride]")
+        lstride = lens.shape[1]
+    offsets = np.zeros(capacity, np.uint64)
+    block_index = np.zeros(capacity, np.uint32)
+    symbol_id = np.zeros(capacity, np.uint16)
+    length = np.zeros(capacity, np.uint16)
+    block_start = np.zeros((nb + 1, 2), np.uint64)
+    N.check(N.lib().nfec_tx_list_host(k, m, vector_size, mask.ctypes.data, mask.shape[1],
+                                      None if nd is None else nd.ctypes.data, nb,
+                                      None if lens is None else lens.ctypes.data, lstride, gap, offsets.ctypes.data,
+                                      block_index.ctypes.data, symbol_id.ctypes.data, length.ctypes.data, capacity,
+                                      block_start.ctypes.data), "nfec_tx_list_host")
+    return offsets, block_index, symbol_id, length, block_start
 
 
 # -- synthetic workload helpers (device kernels) --

@@ -783,6 +783,93 @@ int nfec_decode_received(nfec_codec* codec, const nfec_block_batch* batch, const
     return decode_device(codec, batch, codec->ws.rxlocs.p, lstride, codec->ws.rxcounts.p, status, s, true);
 }
 
+// ---- sender assembly on the device (kernels_tx.hip) ----
+// The argument-check order is the receiver entries': arguments first, then the codec's device.
+int nfec_tx_list(const nfec_codec* codec, const uint32_t* pending, uint32_t mask_stride, const uint16_t* num_data,
+                 uint32_t nblocks, const uint16_t* seg_length, uint32_t length_stride, uint32_t gap, uint64_t* offsets,
+                 uint32_t* block_index, uint16_t* symbol_id, uint16_t* length, uint32_t capacity, uint64_t* block_start,
+                 void* stream)
+{
+    if (!codec) return fail(NFEC_EINVAL, "null codec");
+    if (nblocks) {
+        if (!pending) return fail(NFEC_EINVAL, "null pending mask");
+        int rc = check_mask(codec, pending, mask_stride);
+        if (rc) return rc;
+    }
+    if (seg_length && length_stride < codec->k) return fail(NFEC_EINVAL, "length_stride < k");
+    if (capacity && (!offsets || !block_index || !symbol_id || !length)) return fail(NFEC_EINVAL, "null output array");
+    if (!block_start) return fail(NFEC_EINVAL, "null block_start");
+    if (primary(codec)->host_only) return host_only_fail();
+    const nfec_codec* c = stripe_for(const_cast<nfec_codec*>(codec), nblocks ? (const void*)pending : block_start);
+    if (!c) return fail(NFEC_EINVAL, "pending mask is not on a device of the codec");
+    DeviceGuard g(c->device);
+    TxListArgs a;
+    a.pending = pending;
+    a.mask_stride = mask_stride;
+    a.num_data = num_data;
+    a.k = c->k;
+    a.m = c->m;
+    a.vec = c->vec;
+    a.nblocks = nblocks;
+    a.seg_length = seg_length;
+    a.length_stride = length_stride;
+    a.gap = gap;
+    a.offsets = offsets;
+    a.block_index = block_index;
+    a.symbol_id = symbol_id;
+    a.length = length;
+    a.capacity = capacity;
+    a.block_start = block_start;
+    return launch_tx_list(a, static_cast<hipStream_t>(stream));
+}
+
+int nfec_tx_emit(const nfec_codec* codec, const nfec_block_batch* batch, const nfec_tx_segments* seg, uint8_t fec_id,
+                 uint8_t fec_m, uint32_t first_block_id, uint32_t* pending, uint32_t mask_stride, uint32_t* stats,
+                 void* stream)
+{
+    if (!codec || !batch || !seg) return fail(NFEC_EINVAL, "null codec, batch or segments");
+    int rc = pending ? check_mask(codec, pending, mask_stride) : NFEC_OK;
+    if (rc) return rc;
+    if (seg->count && !seg->payloads) return fail(NFEC_EINVAL, "null segments->payloads");
+    if (seg->count && !seg->offsets) return fail(NFEC_EINVAL, "null segments->offsets");
+    if (seg->count && !seg->block_index) return fail(NFEC_EINVAL, "null segments->block_index");
+    if (seg->count && !seg->symbol_id) return fail(NFEC_EINVAL, "null segments->symbol_id");
+    if (seg->count && !seg->length) return fail(NFEC_EINVAL, "null segments->length");
+    uint32_t id_kind = TX_ID_NONE;
+    if (fec_id) {
+        uint8_t probe[8];
+        if (nfec_payload_id_write(fec_id, fec_m, 0, 0, 0, probe) < 0) return fail(NFEC_EINVAL, "bad fec_id / fec_m");
+        id_kind = fec_id == 129 ? TX_ID_BLOCK32_LEN : fec_id == 2 && fec_m == 16 ? TX_ID_BLOCK16 : TX_ID_BLOCK24;
+    }
+    if ((rc = check_batch(codec, batch)) || batch->nblocks == 0 || seg->count == 0) return rc;
+    const nfec_codec* c = stripe_for(const_cast<nfec_codec*>(codec), batch->blocks);
+    if (!c) return fail(NFEC_EINVAL, "batch is not on a device of the codec");
+    DeviceGuard g(c->device);
+    TxEmitArgs a;
+    a.base = static_cast<const uint8_t*>(batch->blocks);
+    a.block_stride = batch->block_stride;
+    a.seg_stride = batch->seg_stride;
+    a.nblocks = batch->nblocks;
+    a.num_data = batch->num_data;
+    a.k = c->k;
+    a.m = c->m;
+    a.vec = c->vec;
+    a.payloads = static_cast<uint8_t*>(seg->payloads);
+    a.payload_bytes = seg->payload_bytes;
+    a.offsets = seg->offsets;
+    a.block_index = seg->block_index;
+    a.symbol_id = seg->symbol_id;
+    a.length = seg->length;
+    a.count = seg->count;
+    a.count_dev = seg->count_dev;
+    a.id_kind = id_kind;
+    a.first_block_id = first_block_id;
+    a.pending = pending;
+    a.mask_stride = mask_stride;
+    a.stats = stats;
+    return launch_tx_emit(a, static_cast<hipStream_t>(stream));
+}
+
 // ---- per-call NORM semantics (synchronous, host vectors) ----
 // One call = gather the caller's vectors into the codec's pinned staging (host memcpy), one
 // H2D copy, the kernels, one D2H copy of what the call writes, one synchronize, scatter.  The

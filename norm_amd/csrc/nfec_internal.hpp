@@ -776,4 +776,51 @@ struct RxErasureArgs {
 };
 int launch_rx_erasures(const RxErasureArgs& a, hipStream_t s);
 
+// Sender assembly on the device (kernels_tx.hip; nfec.h "sender assembly on the device").
+// List: the pending slots of every block in NextSenderMsg's order, with their payload lengths and
+// packed wire offsets.  Three kernels: per-block counts and byte sums (one wave per block) into
+// block_start, an exclusive scan over the blocks, and the per-block expansion.
+struct TxListArgs {
+    const uint32_t* pending = nullptr;     // [nblocks][mask_stride]
+    uint32_t mask_stride = 0;
+    const uint16_t* num_data = nullptr;    // per block, or null = k
+    uint32_t k = 0, m = 0, vec = 0;
+    uint32_t nblocks = 0;
+    const uint16_t* seg_length = nullptr;  // [nblocks][length_stride], or null = vec
+    uint32_t length_stride = 0;
+    uint32_t gap = 0;
+    uint64_t* offsets = nullptr;
+    uint32_t* block_index = nullptr;
+    uint16_t* symbol_id = nullptr;
+    uint16_t* length = nullptr;
+    uint32_t capacity = 0;
+    uint64_t* block_start = nullptr;       // [nblocks + 1][2]
+};
+int launch_tx_list(const TxListArgs& a, hipStream_t s);
+// Emit: one wave per entry; the 8-byte aligned slot goes to any byte offset of the wire buffer
+// behind its FEC payload ID, and lane 0 clears the slot's pending bit.
+enum { TX_ID_NONE = 0, TX_ID_BLOCK24 = 1, TX_ID_BLOCK16 = 2, TX_ID_BLOCK32_LEN = 3 };
+struct TxEmitArgs {
+    const uint8_t* base = nullptr;         // the batch
+    uint64_t block_stride = 0;
+    uint32_t seg_stride = 0;
+    uint32_t nblocks = 0;
+    const uint16_t* num_data = nullptr;    // per block, or null = k
+    uint32_t k = 0, m = 0, vec = 0;
+    uint8_t* payloads = nullptr;           // the wire buffer
+    uint64_t payload_bytes = 0;
+    const uint64_t* offsets = nullptr;
+    const uint32_t* block_index = nullptr;
+    const uint16_t* symbol_id = nullptr;
+    const uint16_t* length = nullptr;
+    uint32_t count = 0;
+    const uint64_t* count_dev = nullptr;   // device, or null: min(count, *count_dev) entries
+    uint32_t id_kind = TX_ID_NONE;         // the payload ID's layout (TX_ID_*)
+    uint32_t first_block_id = 0;
+    uint32_t* pending = nullptr;           // [nblocks][mask_stride], or null
+    uint32_t mask_stride = 0;
+    uint32_t* stats = nullptr;             // [2] emitted, rejected (or null)
+};
+int launch_tx_emit(const TxEmitArgs& a, hipStream_t s);
+
 }  // namespace nfec

@@ -13,6 +13,11 @@ rx    receiver assembly on the device, RS8 k=64 m=32 vec=1400, 65,536 blocks: 80
       segments arrive (16 source lost), in an order shuffled over the whole batch, payloads at a
       1,413-byte pitch (every alignment occurs).  nfec_rx_place next to nfec_util_stream_copy of the
       same byte count, nfec_decode_received next to nfec_decode on lists built beforehand
+tx    sender assembly on the device, RS8 k=64 m=32 vec=1400, 65,536 blocks: every block's 64 source
+      slots and its first 16 parity slots pending, gap 13 (messages at the rx workload's 1,413-byte
+      pitch, every alignment occurs), fec_id 5.  nfec_tx_list and nfec_tx_emit next to
+      nfec_util_stream_copy of the emitted byte count (--gap / --fec-id for other layouts of the
+      wire buffer: --gap 8 --fec-id 129 makes every message eleven whole 128-byte lines)
 
 Inputs are synthetic (splitmix64 segments generated on the GPU); GiB/s counts source bytes
 (k * vec per block) per pass, like the headline metric.
@@ -46,6 +51,8 @@ def main():
     p.add_argument("--loss", default="source", choices=["source", "uniform"],
                    help="source: erasures among the source segments (the headline pattern); uniform: "
                         "drawn over all k + m segments, as NORM loses source and parity alike")
+    p.add_argument("--gap", type=int, default=13, help="tx: bytes left free in front of every payload")
+    p.add_argument("--fec-id", type=int, default=5, choices=[2, 5, 129], help="tx: the payload ID written (fec_m 8)")
     p.add_argument("--options", type=int, default=0, help="encoder options (NFEC_OPT_*, e.g. the Toeplitz split's levels)")
     a = p.parse_args()
     import torch
@@ -55,6 +62,8 @@ def main():
         return rs8_sweep(a)
     if a.workload == "rx":
         return rx_bench(a)
+    if a.workload == "tx":
+        return tx_bench(a)
 
     shapes = {  # kind, k, m, blocks, erasures (0: encode only)
         "c4": (na.NFEC_RS16, 4096, 256, 4096, 0),
@@ -426,6 +435,119 @@ def rx_bench(a):
         "decode_paths": {nm: c for nm, c in dec.decode_paths().items() if c},
         "rate_note": "GB/s = payload bytes placed (or bytes copied) per second, each byte read once and written once",
         "verified": ok,
+    }), flush=True)
+
+
+def tx_bench(a):
+    """list + emit against the streaming copy of the emitted bytes, one JSON line"""
+    import numpy as np
+    import torch
+    import norm_amd as na
+    from norm_amd import _native as N
+
+    torch.cuda.set_device(0)
+    stream = torch.cuda.current_stream()
+    k, m, vec, gap, fec_id, first_id = a.k or 64, a.m or 32, a.vec, a.gap, a.fec_id, 0xFFFF00
+    idlen = N.lib().nfec_payload_id_length(fec_id)
+    assert gap >= idlen, "--gap must leave room for the payload ID"
+    par = min(m, 16)  # parity slots pending per block
+    nb = a.blocks or 65536
+    n = k + m
+    enc = na.NormEncoderRS8()
+    assert enc.Init(k, m, vec)
+    stride = (vec + 7) & ~7
+    batch = torch.zeros((nb, n, stride), dtype=torch.uint8, device="cuda")
+    na.fill_blocks(batch, k, vec, 0x4E4F524D)
+    enc.encode_blocks(batch, stream=stream)
+    words = (n + 31) // 32
+    row = np.zeros(words, np.uint32)
+    for s in range(k + par):
+        row[s // 32] |= np.uint32(1 << (s % 32))
+    full = torch.from_numpy(np.tile(row, (nb, 1)).view(np.int32)).cuda()
+    pending = full.clone()
+    count = nb * (k + par)
+    nbytes = count * (gap + vec)
+    wire = torch.empty(nbytes + 16, dtype=torch.uint8, device="cuda")
+    wire.fill_(0xA5)
+    offsets = torch.zeros(count, dtype=torch.int64, device="cuda")
+    block_index = torch.zeros(count, dtype=torch.int32, device="cuda")
+    symbol_id = torch.zeros(count, dtype=torch.int16, device="cuda")
+    length = torch.zeros(count, dtype=torch.int16, device="cuda")
+    block_start = torch.zeros((nb + 1, 2), dtype=torch.int64, device="cuda")
+    stats = torch.zeros(2, dtype=torch.int32, device="cuda")
+    emitted = count * (idlen + vec)
+    cbytes = emitted & ~15
+    csrc = torch.empty(cbytes, dtype=torch.uint8, device="cuda")
+    csrc.fill_(0x3C)
+    cdst = torch.empty_like(csrc)
+
+    def timed(fn, before=None):
+        """per-step times (ms) of fn alone: `before` runs untimed ahead of each step"""
+        out = []
+        for i in range(a.warmup + a.steps):
+            if before:
+                before()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            fn()
+            e1.record(stream)
+            e1.synchronize()
+            if i >= a.warmup:
+                out.append(e0.elapsed_time(e1))
+        return out
+
+    def make_list():
+        # the C entry on arrays allocated once: list_pending would time its own allocations too
+        N.check(N.lib().nfec_tx_list(enc._h, pending.data_ptr(), words, None, nb, None, 0, gap, offsets.data_ptr(),
+                                     block_index.data_ptr(), symbol_id.data_ptr(), length.data_ptr(), count,
+                                     block_start.data_ptr(), stream.cuda_stream), "nfec_tx_list")
+
+    def emit(mask, st):
+        enc.emit_segments(batch, wire, offsets, block_index, symbol_id, length, count_dev=block_start[nb, :1],
+                          fec_id=fec_id, first_block_id=first_id, pending=mask, stats=st, stream=stream)
+
+    def med(v):
+        return float(np.median(v))
+
+    list_ms = timed(make_list)
+    totals = block_start[nb].cpu().tolist()
+    emit_ms = timed(lambda: emit(pending, None), before=lambda: pending.copy_(full))
+    cleared = not bool(pending.any())
+    emit_nomask_ms = timed(lambda: emit(None, None))
+    emit_stats_ms = timed(lambda: emit(None, stats), before=lambda: stats.zero_())
+    got_stats = stats.cpu().tolist()
+    copy_ms = timed(lambda: na.stream_copy(cdst, csrc, stream=stream))
+    # a seeded sample of messages against the batch: the payload ID, then the slot's bytes
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(0x4E4F524D)
+    pick = torch.randint(0, count, (min(count, 8192),), device="cuda", generator=gen)
+    pick = torch.cat([pick, torch.tensor([0, count - 1], device="cuda")])
+    off, b, s = offsets[pick], block_index[pick].long(), symbol_id[pick].long() & 0xFFFF
+    rows = wire[(off[:, None] + torch.arange(-idlen, vec, device="cuda")[None, :])]
+    want_id = np.zeros((pick.numel(), idlen), np.uint8)
+    for i, (bb, ss) in enumerate(zip(b.cpu().tolist(), s.cpu().tolist())):  # the wire layer's own bytes
+        assert N.lib().nfec_payload_id_write(fec_id, 8, (first_id + bb) & 0xFFFFFFFF, ss, k,
+                                             want_id[i].ctypes.data) == idlen
+    ok = bool(torch.equal(rows[:, :idlen], torch.from_numpy(want_id).cuda()))
+    ok &= bool(torch.equal(rows[:, idlen:], batch.view(nb * n, stride)[b * n + s, :vec]))
+    ok &= bool((off == (pick + 1) * gap + pick * vec).all())  # the packed offsets
+    ok &= totals == [count, nbytes] and got_stats == [count, 0] and cleared
+    em, cm = med(emit_ms), med(copy_ms)
+    print(json.dumps({
+        "workload": "tx", "codec": "RS8", "k": k, "m": m, "vec": vec, "blocks": nb, "pending_parity_per_block": par,
+        "segments": count, "gap": gap, "fec_id": fec_id, "wire_GB": round(nbytes / 1e9, 3),
+        "emitted_GB": round(emitted / 1e9, 3), "steps": a.steps, "warmup": a.warmup,
+        "list_ms": round(med(list_ms), 4), "list_ms_min": round(min(list_ms), 4),
+        "emit_ms": round(em, 3), "emit_ms_min": round(min(emit_ms), 3),
+        "emit_GBps": round(emitted / (em * 1e-3) / 1e9, 1),
+        "emit_without_mask_ms": round(med(emit_nomask_ms), 3),
+        "emit_with_stats_ms": round(med(emit_stats_ms), 3),
+        "stream_copy_bytes": cbytes, "stream_copy_ms": round(cm, 3), "stream_copy_ms_min": round(min(copy_ms), 3),
+        "stream_copy_GBps": round(cbytes / (cm * 1e-3) / 1e9, 1),
+        "emit_rate_vs_stream_copy": round((emitted / em) / (cbytes / cm), 3),
+        "rate_note": "GB/s = wire bytes written (ID + payload; or bytes copied) per second, each byte read once "
+                     "and written once",
+        "sampled_messages": int(pick.numel()), "verified": ok,
     }), flush=True)
 
 

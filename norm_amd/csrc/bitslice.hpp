@@ -197,11 +197,14 @@ __device__ __forceinline__ void make_dec_items(const DecArgs& a, uint32_t item_b
     it.rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(it.wbase), (short)0, (int)0x80000000u, 0x00020000);
     it.item_base = item_base;
     it.need = 0;
+    // (the launch rounds the item groups up to whole workgroups: a wave whose item_base is past
+    // the last item stands on the last one, so that its emask reads stay inside the batch's rows)
+    const uint32_t spare = min(item_base, total - 1);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const uint32_t g = item_base + (uint32_t)i * 64u + lane;
         const bool ok = g < total;
-        const uint32_t gg = ok ? g : item_base;
+        const uint32_t gg = ok ? g : spare;
         const uint32_t b = gg / ips;
         const uint32_t o = gg - b * ips;
         it.off[i] = (uint32_t)((b - b0) * a.block_stride) + o * 8u;

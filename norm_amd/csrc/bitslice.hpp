@@ -293,7 +293,12 @@ int launch_mdp_q4_encode(uint32_t k, uint32_t m, const bs::EncArgs& a, hipStream
 // rs8_enc_d2.hip: (64, 32) with 2 role waves of 16 rows at 3 waves per SIMD (LDS-DMA column ring);
 // NFEC_ENOTSUP for every other shape and for the layouts launch_rs8_q4_encode keeps
 int launch_rs8_d2_encode(uint32_t k, uint32_t m, const bs::EncArgs& a, hipStream_t s);
+// rs8_enc_t3.hip: (64, 32) with 3 role waves at 3 waves per SIMD, one Karatsuba step over the
+// generator's Toeplitz core; takes and refuses exactly launch_rs8_d2_encode's batches
+int launch_rs8_t3_encode(uint32_t k, uint32_t m, const bs::EncArgs& a, hipStream_t s);
 #ifdef NFEC_DIAG
+// gen_rs8_t3.hip (diagnostic library): its timing probes, NFEC_ENOTSUP unless NFEC_T3_VARIANT selects one
+int launch_rs8_t3_probe(uint32_t k, uint32_t m, const bs::EncArgs& a, hipStream_t s);
 // gen_rs8_d2.hip (diagnostic library): its timing probes, NFEC_ENOTSUP unless NFEC_D2_VARIANT selects one
 int launch_rs8_d2_probe(uint32_t k, uint32_t m, const bs::EncArgs& a, hipStream_t s);
 #endif

@@ -550,16 +550,21 @@ int fixed_then_tail(const nfec_codec* c, const nfec_block_batch* b, bs::EncArgs 
     return launch_encode_tail(ta, c->vec, s);
 }
 
-// (64, 32): the 2-role-wave kernel at 3 waves per SIMD (rs8_enc_d2.hip) for the layouts it takes,
-// every other shape and layout the 4-role-wave kernels (NFEC_ENC_D2=0, diagnostic library: off;
-// read per call, so one process can run both)
+// (64, 32): the 3-role-wave Karatsuba kernel at 3 waves per SIMD (rs8_enc_t3.hip) for the layouts
+// it takes, every other shape and layout the 4-role-wave kernels.  The 2-role-wave kernel
+// (rs8_enc_d2.hip) takes exactly t3's batches and is reached only with t3 switched off
+// (NFEC_ENC_T3=0 / NFEC_ENC_D2=0, diagnostic library: off; read per call, so one process can run
+// all three)
 int launch_rs8_d2_or_q4(uint32_t k, uint32_t m, const bs::EncArgs& e, hipStream_t s)
 {
+    const bool use_t3 = diag_knob("NFEC_ENC_T3", 1) != 0;
     const bool use_d2 = diag_knob("NFEC_ENC_D2", 1) != 0;
     int rc = NFEC_ENOTSUP;
 #ifdef NFEC_DIAG
-    if (use_d2) rc = launch_rs8_d2_probe(k, m, e, s);  // NFEC_D2_VARIANT: a timing probe
+    if (use_t3) rc = launch_rs8_t3_probe(k, m, e, s);  // NFEC_T3_VARIANT: a timing probe
+    if (rc == NFEC_ENOTSUP && use_d2) rc = launch_rs8_d2_probe(k, m, e, s);  // NFEC_D2_VARIANT
 #endif
+    if (rc == NFEC_ENOTSUP && use_t3) rc = launch_rs8_t3_encode(k, m, e, s);
     if (rc == NFEC_ENOTSUP && use_d2) rc = launch_rs8_d2_encode(k, m, e, s);
     if (rc == NFEC_ENOTSUP) rc = launch_rs8_q4_encode(k, m, e, s);
     return rc;

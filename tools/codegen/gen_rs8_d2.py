@@ -123,10 +123,8 @@ def column(G, r0, j, w, first):
     return pre, ups
 
 
-def role_asm(G, w, probe=None):
-    noload, nocompute, noexch = probe == "noload", probe == "nocompute", probe == "noexch"
-    r0 = w * ROWS
-    steps = K // NW
+def setup():
+    """the DMA and store descriptors and the transpose masks"""
     L = [f"s_mov_b64 s[{S_IB}:{S_IB + 1}], %[ib]",
          f"s_mov_b32 s{S_LRS + 2}, 0x80000000",   # offsets with bit 31 set (pairs past the batch) read nothing
          f"s_mov_b32 s{S_LRS + 3}, 0x00020000",
@@ -135,6 +133,66 @@ def role_asm(G, w, probe=None):
          f"s_mov_b32 s{S_SRS + 3}, 0x00020000"]
     for i, mk in enumerate(MASKS):
         L.append(f"s_mov_b32 s{S_MASK + i}, 0x{mk:08x}")
+    return L
+
+
+def epilogue(r0, w, before_row=None, park=park):
+    """rows [r0, r0 + ROWS) out of the accumulators; w: whose parked offsets (park: where they lie).
+    before_row(n, r): code ahead of the n-th stored row r (gen_rs8_t3.py merges another wave's
+    share there)"""
+    L = []
+    # epilogue as q4's: per row, planes back to bytes, optional accumulate, stores.  A lane's pair is
+    # 16 contiguous bytes, so a whole pair goes out as one buffer_store_dwordx4 (a wave's store is
+    # then 1 KiB of whole lines; two dwordx2 stores at a 16-byte lane stride would each half-fill
+    # them), staged through a 4-aligned register quad: the first row stored (row 8, by dwordx2)
+    # frees banks 2/3 of the quads QUADS.  The first item of a half-valid pair goes out by dwordx2,
+    # behind a branch that is not taken when no lane of the wave holds one.
+    so = [SO_D[0], SO_H[0], SO_D[1], SO_H[1]]   # items in X's dword-pair order: (pair 0, half 0), (0, 1), (1, 0), (1, 1)
+    L += [f"ds_read_b64 v[{SO_D[0]}:{SO_D[1]}], %[la] offset:{park(w, 0)}",
+          f"ds_read_b64 v[{SO_H[0]}:{SO_H[1]}], %[la] offset:{park(w, 1)}",
+          "s_waitcnt lgkmcnt(0)"]
+    for p in range(2):
+        # whole pair: d, dropped (bit 31) unless h is valid; half pair: d, dropped unless h is not
+        L += [f"v_and_or_b32 v{SO_F[p]}, v{SO_H[p]}, s{S_SRS + 2}, v{SO_D[p]}",
+              f"v_not_b32 v{SO_E[p]}, v{SO_H[p]}",
+              f"v_and_or_b32 v{SO_E[p]}, v{SO_E[p]}, s{S_SRS + 2}, v{SO_D[p]}",
+              f"v_cmp_le_i32 vcc, 0, v{SO_E[p]}",
+              f"s_mov_b64 s[{S_HALF}:{S_HALF + 1}], vcc" if p == 0 else f"s_or_b64 s[{S_HALF}:{S_HALF + 1}], s[{S_HALF}:{S_HALF + 1}], vcc"]
+    for n, r in enumerate(EPI_ROWS):
+        acc = [f3_acc(r, i) for i in range(8)]
+        if before_row:
+            L += before_row(n, r)
+        L += f3_blk(transpose(acc, epi_pool))
+        L += [f"s_mul_i32 s{S_ROW}, %[ss], {K + r0 + r}", "s_cmp_eq_u32 %[acc], 0", f"s_cbranch_scc1 Lnoacc{r}_%="]
+        for q in range(4):
+            L.append(f"buffer_load_dwordx2 v[{X[2 * q]}:{X[2 * q + 1]}], v{so[q]}, s[{S_SRS}:{S_SRS + 3}], s{S_ROW} offen")
+        L.append("s_waitcnt vmcnt(0)")
+        for q in range(4):
+            L.append(f"v_xor_b32 v{acc[2 * q]}, v{X[2 * q]}, v{acc[2 * q]}")
+            L.append(f"v_xor_b32 v{acc[2 * q + 1]}, v{X[2 * q + 1]}, v{acc[2 * q + 1]}")
+        L.append(f"Lnoacc{r}_%=:")
+        if n == 0:
+            assert set(acc) >= {x for q in QUADS for x in q[2:]}
+            for q in range(4):
+                L.append(f"buffer_store_dwordx2 v[{acc[2 * q]}:{acc[2 * q + 1]}], v{so[q]}, s[{S_SRS}:{S_SRS + 3}], s{S_ROW} offen")
+            continue
+        for p in range(2):
+            Q = QUADS[p]
+            L += [f"v_mov_b32 v{Q[i]}, v{acc[4 * p + i]}" for i in range(4)]
+            # (a store of more than 8 bytes needs a wait state before its data registers change)
+            L += [f"buffer_store_dwordx4 v[{Q[0]}:{Q[3]}], v{SO_F[p]}, s[{S_SRS}:{S_SRS + 3}], s{S_ROW} offen", "s_nop 1"]
+        L += [f"s_cmp_lg_u64 s[{S_HALF}:{S_HALF + 1}], 0", f"s_cbranch_scc0 Lnohalf{r}_%="]
+        for p in range(2):
+            L.append(f"buffer_store_dwordx2 v[{acc[4 * p]}:{acc[4 * p + 1]}], v{SO_E[p]}, s[{S_SRS}:{S_SRS + 3}], s{S_ROW} offen")
+        L.append(f"Lnohalf{r}_%=:")
+    return L
+
+
+def role_asm(G, w, probe=None):
+    noload, nocompute, noexch = probe == "noload", probe == "nocompute", probe == "noexch"
+    r0 = w * ROWS
+    steps = K // NW
+    L = setup()
 
     def read_dp():
         return [] if noload else [f"ds_read_b64 v[{DP[0]}:{DP[1]}], %[la] offset:{park(w, 0)}"]
@@ -202,49 +260,7 @@ def role_asm(G, w, probe=None):
             L.append("s_waitcnt lgkmcnt(0)")
         pre, ups = column(G, r0, NW * s + 1 - w, Y, first=False)
         L += pre + ups
-    # epilogue as q4's: per row, planes back to bytes, optional accumulate, stores.  A lane's pair is
-    # 16 contiguous bytes, so a whole pair goes out as one buffer_store_dwordx4 (a wave's store is
-    # then 1 KiB of whole lines; two dwordx2 stores at a 16-byte lane stride would each half-fill
-    # them), staged through a 4-aligned register quad: the first row stored (row 8, by dwordx2)
-    # frees banks 2/3 of the quads QUADS.  The first item of a half-valid pair goes out by dwordx2,
-    # behind a branch that is not taken when no lane of the wave holds one.
-    so = [SO_D[0], SO_H[0], SO_D[1], SO_H[1]]   # items in X's dword-pair order: (pair 0, half 0), (0, 1), (1, 0), (1, 1)
-    L += [f"ds_read_b64 v[{SO_D[0]}:{SO_D[1]}], %[la] offset:{park(w, 0)}",
-          f"ds_read_b64 v[{SO_H[0]}:{SO_H[1]}], %[la] offset:{park(w, 1)}",
-          "s_waitcnt lgkmcnt(0)"]
-    for p in range(2):
-        # whole pair: d, dropped (bit 31) unless h is valid; half pair: d, dropped unless h is not
-        L += [f"v_and_or_b32 v{SO_F[p]}, v{SO_H[p]}, s{S_SRS + 2}, v{SO_D[p]}",
-              f"v_not_b32 v{SO_E[p]}, v{SO_H[p]}",
-              f"v_and_or_b32 v{SO_E[p]}, v{SO_E[p]}, s{S_SRS + 2}, v{SO_D[p]}",
-              f"v_cmp_le_i32 vcc, 0, v{SO_E[p]}",
-              f"s_mov_b64 s[{S_HALF}:{S_HALF + 1}], vcc" if p == 0 else f"s_or_b64 s[{S_HALF}:{S_HALF + 1}], s[{S_HALF}:{S_HALF + 1}], vcc"]
-    for n, r in enumerate(EPI_ROWS):
-        acc = [f3_acc(r, i) for i in range(8)]
-        L += f3_blk(transpose(acc, epi_pool))
-        L += [f"s_mul_i32 s{S_ROW}, %[ss], {K + r0 + r}", "s_cmp_eq_u32 %[acc], 0", f"s_cbranch_scc1 Lnoacc{r}_%="]
-        for q in range(4):
-            L.append(f"buffer_load_dwordx2 v[{X[2 * q]}:{X[2 * q + 1]}], v{so[q]}, s[{S_SRS}:{S_SRS + 3}], s{S_ROW} offen")
-        L.append("s_waitcnt vmcnt(0)")
-        for q in range(4):
-            L.append(f"v_xor_b32 v{acc[2 * q]}, v{X[2 * q]}, v{acc[2 * q]}")
-            L.append(f"v_xor_b32 v{acc[2 * q + 1]}, v{X[2 * q + 1]}, v{acc[2 * q + 1]}")
-        L.append(f"Lnoacc{r}_%=:")
-        if n == 0:
-            assert set(acc) >= {x for q in QUADS for x in q[2:]}
-            for q in range(4):
-                L.append(f"buffer_store_dwordx2 v[{acc[2 * q]}:{acc[2 * q + 1]}], v{so[q]}, s[{S_SRS}:{S_SRS + 3}], s{S_ROW} offen")
-            continue
-        for p in range(2):
-            Q = QUADS[p]
-            L += [f"v_mov_b32 v{Q[i]}, v{acc[4 * p + i]}" for i in range(4)]
-            # (a store of more than 8 bytes needs a wait state before its data registers change)
-            L += [f"buffer_store_dwordx4 v[{Q[0]}:{Q[3]}], v{SO_F[p]}, s[{S_SRS}:{S_SRS + 3}], s{S_ROW} offen", "s_nop 1"]
-        L += [f"s_cmp_lg_u64 s[{S_HALF}:{S_HALF + 1}], 0", f"s_cbranch_scc0 Lnohalf{r}_%="]
-        for p in range(2):
-            L.append(f"buffer_store_dwordx2 v[{acc[4 * p]}:{acc[4 * p + 1]}], v{SO_E[p]}, s[{S_SRS}:{S_SRS + 3}], s{S_ROW} offen")
-        L.append(f"Lnohalf{r}_%=:")
-    return L
+    return L + epilogue(r0, w)
 
 
 # the committed source's compact form (gen_fdec_asm.py f3_compact): one macro per instruction shape

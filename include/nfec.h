@@ -28,6 +28,9 @@
  *   nfec_tx_list / nfec_tx_emit
  *                         the pending walk, the payload lengths, the FEC payload ID and UnsetPending
  *                         of NormObject::NextSenderMsg  src/common/normObject.cpp:1877-2078
+ *   nfec_object_layout_for / nfec_object_read / nfec_object_write
+ *                         the block partition of NormObject::Open  src/common/normObject.cpp:134-137,
+ *                         :203-231, NormDataObject::ReadSegment :2673-2718 and WriteSegment :2628-2670
  *   nfec_encode_host_vectors / nfec_decode_host_vectors
  *                         the same two sites on NORM's scattered segment lists (block->SegmentList())
  *   nfec_encode_segment   NormEncoder::Encode(segmentId, dataVector, parityVectorList)
@@ -346,6 +349,98 @@ typedef struct nfec_tx_segments {      /* device arrays, as nfec_tx_list writes 
 int nfec_tx_emit(const nfec_codec* codec, const nfec_block_batch* batch, const nfec_tx_segments* segments,
                  uint8_t fec_id, uint8_t fec_m, uint32_t first_block_id, uint32_t* pending,
                  uint32_t mask_stride, uint32_t* stats, void* stream);
+
+/* ---- object segmentation on the device ----
+ * The mapping between a NORM data object (a contiguous run of bytes) and the source slots of its
+ * FEC blocks: one step before nfec_encode on the sender, one step after nfec_decode_received on
+ * the receiver.  In the reference it is NormObject::Open's block partition
+ * (src/common/normObject.cpp:134-137, :203-231; NORM spec 5.1.1, the RFC 5052 large / small
+ * blocks), NormDataObject::ReadSegment (:2673-2718) with the zero pad of CalculateBlockParity
+ * (:2203-2229) on the sender, and NormDataObject::WriteSegment (:2628-2670) on the receiver, which
+ * is called for every received source segment (:1529) and for every repaired one after a
+ * successful Decode (:1616).  Non-stream objects only: the entries take no object type.
+ *
+ * The partition.  num_segments = ceil(object_size / segment_size) and num_blocks =
+ * ceil(num_segments / num_data) (NormObjectSize's divide rounds up everywhere); large_block_size =
+ * ceil(num_segments / num_blocks).  When num_segments == num_blocks * large_block_size every block
+ * has that size and the layout says so the way the reference does: large_block_count = 0,
+ * small_block_size = large_block_size, small_block_count = num_blocks.  Otherwise small_block_size
+ * = large_block_size - 1, large_block_count = num_segments - num_blocks * small_block_size and
+ * small_block_count = num_blocks - large_block_count.  Block b holds
+ * b < large_block_count ? large_block_size : small_block_size segments (GetBlockSize); the large
+ * blocks come first.  final_block_id = num_blocks - 1, and final_segment_size = object_size -
+ * (num_segments - 1) * segment_size is the length of its last segment. */
+typedef struct nfec_object_layout {
+    uint64_t object_size;        /* bytes */
+    uint32_t segment_size;       /* bytes of object per source segment */
+    uint32_t num_data;           /* k the object was opened with */
+    uint64_t num_segments;       /* ceil(object_size / segment_size) */
+    uint32_t num_blocks;         /* ceil(num_segments / num_data) */
+    uint32_t large_block_size, large_block_count;
+    uint32_t small_block_size, small_block_count;
+    uint32_t final_block_id, final_segment_size;
+} nfec_object_layout;
+
+/* Open's arithmetic.  Host only: no GPU, no codec.  NFEC_EINVAL for a null out, for object_size,
+ * segment_size or num_data of 0, segment_size > 65535 or num_data > 65535; NFEC_ERANGE when
+ * num_blocks does not fit 32 bits (Open refuses the object, :145). */
+int nfec_object_layout_for(uint64_t object_size, uint32_t segment_size, uint32_t num_data,
+                           nfec_object_layout* out);
+/* ReadSegment's / WriteSegment's rule for segment `segment` of block `block`: its byte offset in
+ * the object, large_block_size * segment_size * block + segment_size * segment below
+ * large_block_count and large_block_size * segment_size * large_block_count + small_block_size *
+ * segment_size * (block - large_block_count) + segment_size * segment from it on, and its length,
+ * segment_size except final_segment_size for the last segment of final_block_id.  Either output
+ * may be NULL.  NFEC_ERANGE for a block or a segment outside the object.  Host only. */
+int nfec_object_segment(const nfec_object_layout* layout, uint32_t block, uint32_t segment,
+                        uint64_t* offset, uint32_t* length);
+/* num_data_out[i] = the size of block first_block + i, i < nblocks (host array): the num_data[]
+ * of a batch that holds those blocks.  NFEC_ERANGE when first_block + nblocks > num_blocks. */
+int nfec_object_block_sizes(const nfec_object_layout* layout, uint32_t first_block, uint32_t nblocks,
+                            uint16_t* num_data_out);
+
+/* The two device entries.  Batch block i is object block first_block + i and nd_i its size by the
+ * layout; batch->num_data and batch->flags are ignored.  object (device memory, object_bytes of
+ * it) may have any byte alignment; the batch obeys the usual 8-byte rules.  Both calls are
+ * asynchronous on stream, run on the codec device that holds the batch, touch no codec state and
+ * may run concurrently with anything.  NFEC_EINVAL for a null pointer (except the optional
+ * arguments named below), layout->num_data != k, segment_size > vector_size, first_block +
+ * nblocks > num_blocks, a mask_stride below (k + m + 31) / 32 when received is given, a
+ * length_stride below k when seg_length_out is given, or object and batch in device memory of
+ * different devices.  nblocks == 0 is NFEC_OK and launches nothing.
+ *
+ * nfec_object_read (sender): for every s < nd_i, with (off, len) from nfec_object_segment's rule,
+ * the slot's bytes [0, len) become object[off, off + len) and its bytes [len, vector_size) zero
+ * (CalculateBlockParity's pad; for segment_size + 8 == vector_size it covers the 8 bytes NORM
+ * reserves for the stream payload header).  Bytes [vector_size, seg_stride) of a slot and the
+ * slots [nd_i, k + m) are never written, and the object is only read: in aligned 16-byte chunks
+ * that each hold at least one byte of it, so no load leaves a page the object touches.
+ * num_data_out (device [nblocks], may be NULL): num_data_out[i] = nd_i.  seg_length_out (device
+ * [nblocks][length_stride], may be NULL): seg_length_out[i][s] = len for s < nd_i; entries at or
+ * past nd_i are not written.  These are the arrays nfec_encode (batch.num_data) and nfec_tx_list
+ * take.  NFEC_EINVAL unless object_bytes >= object_size (ReadSegment would return 0 and fail the
+ * block).
+ *
+ * nfec_object_write (receiver): segment (i, s), s < nd_i, is written when received is NULL, or
+ * its bit is set in received[i] (the reception mask's layout), or status is given and status[i] >
+ * 0 (nfec_decode's status of a repaired block): received source segments are delivered, erased
+ * ones only after a successful Decode.  A written segment stores the first len' bytes of its slot
+ * to object[off, off + len'), len' being len clamped at object_bytes as WriteSegment clamps at
+ * data_max (:2664-2667): nothing at all when off >= object_bytes.  No other byte of the object is
+ * written, or read and written back: the neighbouring segment, which shares 16-byte pieces and
+ * cache lines, may be unselected, hold an earlier call's bytes or be written by another wave at
+ * the same time.  No byte outside a slot's own seg_stride bytes is read; the batch and the mask
+ * are only read.  stats (device [2], may be NULL; the caller zeroes it): the selected and the
+ * not-selected segment counts are added to stats[0..1] (a selected segment wholly past
+ * object_bytes counts as selected, as WriteSegment returns true for it). */
+int nfec_object_read(const nfec_codec* codec, const nfec_object_layout* layout, const void* object,
+                     uint64_t object_bytes, uint32_t first_block, const nfec_block_batch* batch,
+                     uint16_t* num_data_out, uint16_t* seg_length_out, uint32_t length_stride,
+                     void* stream);
+int nfec_object_write(const nfec_codec* codec, const nfec_object_layout* layout, void* object,
+                      uint64_t object_bytes, uint32_t first_block, const nfec_block_batch* batch,
+                      const uint32_t* received, uint32_t mask_stride, const int32_t* status,
+                      uint32_t* stats, void* stream);
 
 /* ---- host-resident batched path: same layouts, host pointers (pageable or pinned).
  * Staged through pinned buffers with H2D / compute / D2H overlapped on streams.

@@ -74,6 +74,23 @@ class TxSegments(ctypes.Structure):
     ]
 
 
+class ObjectLayout(ctypes.Structure):
+    """nfec_object_layout: the FEC block partition of a NORM data object."""
+    _fields_ = [
+        ("object_size", ctypes.c_uint64),
+        ("segment_size", ctypes.c_uint32),
+        ("num_data", ctypes.c_uint32),
+        ("num_segments", ctypes.c_uint64),
+        ("num_blocks", ctypes.c_uint32),
+        ("large_block_size", ctypes.c_uint32),
+        ("large_block_count", ctypes.c_uint32),
+        ("small_block_size", ctypes.c_uint32),
+        ("small_block_count", ctypes.c_uint32),
+        ("final_block_id", ctypes.c_uint32),
+        ("final_segment_size", ctypes.c_uint32),
+    ]
+
+
 class CodecInfo(ctypes.Structure):
     _fields_ = [
         ("kind", ctypes.c_int32),
@@ -172,6 +189,13 @@ _SIGS = {
     "nfec_tx_list_host": (_I, [_U32, _U32, _U32, _P, _U32, _P, _U32, _P, _U32, _U32, _P, _P, _P, _P, _U32, _P]),
     "nfec_tx_emit": (_I, [_P, ctypes.POINTER(BlockBatch), ctypes.POINTER(TxSegments), _U8, _U8, _U32, _P, _U32, _P,
                           _P]),
+    "nfec_object_layout_for": (_I, [_U64, _U32, _U32, ctypes.POINTER(ObjectLayout)]),
+    "nfec_object_segment": (_I, [ctypes.POINTER(ObjectLayout), _U32, _U32, ctypes.POINTER(_U64), ctypes.POINTER(_U32)]),
+    "nfec_object_block_sizes": (_I, [ctypes.POINTER(ObjectLayout), _U32, _U32, _P]),
+    "nfec_object_read": (_I, [_P, ctypes.POINTER(ObjectLayout), _P, _U64, _U32, ctypes.POINTER(BlockBatch), _P, _P, _U32,
+                              _P]),
+    "nfec_object_write": (_I, [_P, ctypes.POINTER(ObjectLayout), _P, _U64, _U32, ctypes.POINTER(BlockBatch), _P, _U32,
+                               _P, _P, _P]),
     "nfec_encode_host": (_I, [_P, ctypes.POINTER(BlockBatch)]),
     "nfec_decode_host": (_I, [_P, ctypes.POINTER(BlockBatch), _P, _U32, _P, _P]),
     "nfec_encode_host_vectors": (_I, [_P, _P, _U32, _P, _U32]),

@@ -324,6 +324,56 @@ class _Codec:
                                      pending.shape[1] if pending is not None else 0, _tensor_ptr(stats, "stats"),
                                      _stream_handle(stream)), "nfec_tx_emit")
 
+    # -- object segmentation on the device (nfec.h, "object segmentation on the device") --
+    def _object_call(self, obj, layout, blocks):
+        self._need()
+        if obj.element_size() != 1 or not obj.is_cuda or not obj.is_contiguous():
+            raise ValueError("obj must be a contiguous uint8 CUDA (HIP) tensor")
+        if not isinstance(layout, N.ObjectLayout):
+            raise ValueError("layout must come from object_layout()")
+        return _batch_struct(blocks, None, False)
+
+    def read_object(self, obj, layout, blocks, first_block=0, num_data=None, seg_length=None, stream=None):
+        """Fill the source slots of a device batch from a NORM data object in device memory
+        (nfec_object_read: ReadSegment and CalculateBlockParity's zero pad).  obj: uint8 tensor that
+        holds the object from its element 0 on, at any byte alignment; layout: object_layout();
+        batch block i is object block first_block + i.  num_data: 16-bit tensor [nblocks] that
+        receives the blocks' sizes (encode_blocks' num_data), or None; seg_length: 16-bit tensor
+        [nblocks, >= k] that receives the source segments' lengths (list_pending's seg_length), or
+        None.  Parity slots and stride padding keep their bytes."""
+        b = self._object_call(obj, layout, blocks)
+        lstride = 0
+        if seg_length is not None:
+            if seg_length.dim() != 2 or seg_length.element_size() != 2 or seg_length.shape[0] != blocks.shape[0]:
+                raise ValueError("seg_length must be a 16-bit tensor [nblocks, length_stride]")
+            lstride = seg_length.shape[1]
+        if num_data is not None and (num_data.element_size() != 2 or num_data.numel() < blocks.shape[0]):
+            raise ValueError("num_data must be a 16-bit tensor [nblocks]")
+        N.check(N.lib().nfec_object_read(self._h, ctypes.byref(layout), _tensor_ptr(obj, "obj"), obj.numel(),
+                                         first_block, ctypes.byref(b), _tensor_ptr(num_data, "num_data"),
+                                         _tensor_ptr(seg_length, "seg_length"), lstride, _stream_handle(stream)),
+                "nfec_object_read")
+
+    def write_object(self, obj, layout, blocks, first_block=0, received=None, status=None, stats=None, stream=None):
+        """Deliver source slots of a device batch to their bytes of a NORM data object in device
+        memory (nfec_object_write: WriteSegment).  A segment is written when received is None, when
+        its bit is set in the reception mask `received`, or when status (decode_received's int32
+        [nblocks]) is positive for its block; obj.numel() bounds the writes as data_max does.  No
+        other byte of obj changes.  stats: int32 [2] the selected and not-selected segment counts
+        are added to (zero it first), or None."""
+        b = self._object_call(obj, layout, blocks)
+        if received is not None:
+            _mask_check(received, blocks.shape[0])
+        if status is not None and (status.element_size() != 4 or status.numel() < blocks.shape[0]):
+            raise ValueError("status must be a 32-bit tensor [nblocks]")
+        if stats is not None and (stats.element_size() != 4 or stats.numel() < 2):
+            raise ValueError("stats must hold two 32-bit counters")
+        N.check(N.lib().nfec_object_write(self._h, ctypes.byref(layout), _tensor_ptr(obj, "obj"), obj.numel(),
+                                          first_block, ctypes.byref(b), _tensor_ptr(received, "received"),
+                                          received.shape[1] if received is not None else 0,
+                                          _tensor_ptr(status, "status"), _tensor_ptr(stats, "stats"),
+                                          _stream_handle(stream)), "nfec_object_write")
+
     def _need(self):
         if not self._h:
             raise RuntimeError("codec not initialised (call Init)")
@@ -625,6 +675,34 @@ def tx_list_host(k, m, vector_size, pending, num_data=None, seg_length=None, gap
                                       block_index.ctypes.data, symbol_id.ctypes.data, length.ctypes.data, capacity,
                                       block_start.ctypes.data), "nfec_tx_list_host")
     return offsets, block_index, symbol_id, length, block_start
+
+
+# -- object segmentation helpers (host rules, no GPU) --
+def object_layout(object_size, segment_size, k):
+    """nfec_object_layout_for: NormObject::Open's FEC block partition of a data object of object_size
+    bytes in segments of segment_size bytes and blocks of at most k segments.  Returns the
+    nfec_object_layout (fields as in include/nfec.h) that read_object / write_object take."""
+    out = N.ObjectLayout()
+    N.check(N.lib().nfec_object_layout_for(object_size, segment_size, k, ctypes.byref(out)), "nfec_object_layout_for")
+    return out
+
+
+def object_segment(layout, block, segment):
+    """nfec_object_segment: (byte offset in the object, length) of a block's segment."""
+    off, length = ctypes.c_uint64(), ctypes.c_uint32()
+    N.check(N.lib().nfec_object_segment(ctypes.byref(layout), block, segment, ctypes.byref(off), ctypes.byref(length)),
+            "nfec_object_segment")
+    return off.value, length.value
+
+
+def object_block_sizes(layout, first_block, nblocks):
+    """nfec_object_block_sizes: NumPy uint16 [nblocks], the sizes of blocks first_block ... of the object."""
+    import numpy as np
+
+    out = np.zeros(nblocks, np.uint16)
+    N.check(N.lib().nfec_object_block_sizes(ctypes.byref(layout), first_block, nblocks, out.ctypes.data),
+            "nfec_object_block_sizes")
+    return out
 
 
 # -- synthetic workload helpers (device kernels) --

@@ -870,6 +870,106 @@ int nfec_tx_emit(const nfec_codec* codec, const nfec_block_batch* batch, const n
     return launch_tx_emit(a, static_cast<hipStream_t>(stream));
 }
 
+// ---- object segmentation on the device (kernels_obj.hip) ----
+// Arguments first, then the codec's device, as above.  The layout is taken only as
+// nfec_object_layout_for makes it: the kernels index the object and the batch by its fields, so a
+// layout that is not one cannot make a call read or write outside either.
+static int check_object_call(const nfec_codec* codec, const nfec_object_layout* layout, const void* object,
+                             const nfec_block_batch* batch, uint32_t first_block)
+{
+    if (!codec || !layout || !batch) return fail(NFEC_EINVAL, "null codec, layout or batch");
+    if (!object) return fail(NFEC_EINVAL, "null object");
+    nfec_object_layout want;
+    if (nfec_object_layout_for(layout->object_size, layout->segment_size, layout->num_data, &want) != NFEC_OK ||
+        want.num_segments != layout->num_segments || want.num_blocks != layout->num_blocks ||
+        want.large_block_size != layout->large_block_size || want.large_block_count != layout->large_block_count ||
+        want.small_block_size != layout->small_block_size || want.small_block_count != layout->small_block_count ||
+        want.final_block_id != layout->final_block_id || want.final_segment_size != layout->final_segment_size)
+        return fail(NFEC_EINVAL, "layout is not one nfec_object_layout_for made");
+    if (layout->num_data != codec->k) return fail(NFEC_EINVAL, "layout->num_data != k");
+    if (layout->segment_size > codec->vec) return fail(NFEC_EINVAL, "segment_size > vector_size");
+    if ((uint64_t)first_block + batch->nblocks > layout->num_blocks)
+        return fail(NFEC_EINVAL, "first_block + nblocks > num_blocks");
+    return NFEC_OK;
+}
+
+// the stripe that holds the batch; an object in another device's memory is refused where HIP can tell
+static const nfec_codec* object_stripe(const nfec_codec* codec, const void* object, const nfec_block_batch* batch)
+{
+    const nfec_codec* c = stripe_for(const_cast<nfec_codec*>(codec), batch->blocks);
+    if (!c) {
+        fail(NFEC_EINVAL, "batch is not on a device of the codec");
+        return nullptr;
+    }
+    hipPointerAttribute_t ao, ab;
+    std::memset(&ao, 0, sizeof(ao));
+    std::memset(&ab, 0, sizeof(ab));
+    if (hipPointerGetAttributes(&ao, object) != hipSuccess || hipPointerGetAttributes(&ab, batch->blocks) != hipSuccess) {
+        (void)hipGetLastError();
+        fail(NFEC_EINVAL, "object is not memory HIP knows");
+        return nullptr;
+    }
+    if (ao.type == hipMemoryTypeDevice && ab.type == hipMemoryTypeDevice && ao.device != ab.device) {
+        fail(NFEC_EINVAL, "object and batch are on different devices");
+        return nullptr;
+    }
+    return c;
+}
+
+static void object_args(ObjArgs& a, const nfec_codec* c, const nfec_object_layout* layout, const void* object,
+                        uint64_t object_bytes, uint32_t first_block, const nfec_block_batch* batch)
+{
+    a.base = static_cast<uint8_t*>(batch->blocks);
+    a.block_stride = batch->block_stride;
+    a.seg_stride = batch->seg_stride;
+    a.nblocks = batch->nblocks;
+    a.vec = c->vec;
+    a.object = static_cast<uint8_t*>(const_cast<void*>(object));
+    a.object_bytes = object_bytes;
+    a.first_block = first_block;
+    a.lay = *layout;
+}
+
+int nfec_object_read(const nfec_codec* codec, const nfec_object_layout* layout, const void* object, uint64_t object_bytes,
+                     uint32_t first_block, const nfec_block_batch* batch, uint16_t* num_data_out,
+                     uint16_t* seg_length_out, uint32_t length_stride, void* stream)
+{
+    int rc = check_object_call(codec, layout, object, batch, first_block);
+    if (rc) return rc;
+    if (object_bytes < layout->object_size) return fail(NFEC_EINVAL, "object_bytes < object_size");
+    if (seg_length_out && length_stride < codec->k) return fail(NFEC_EINVAL, "length_stride < k");
+    if ((rc = check_batch(codec, batch)) || batch->nblocks == 0) return rc;
+    const nfec_codec* c = object_stripe(codec, object, batch);
+    if (!c) return NFEC_EINVAL;
+    DeviceGuard g(c->device);
+    ObjArgs a;
+    object_args(a, c, layout, object, object_bytes, first_block, batch);
+    a.num_data_out = num_data_out;
+    a.seg_length_out = seg_length_out;
+    a.length_stride = length_stride;
+    return launch_obj_read(a, static_cast<hipStream_t>(stream));
+}
+
+int nfec_object_write(const nfec_codec* codec, const nfec_object_layout* layout, void* object, uint64_t object_bytes,
+                      uint32_t first_block, const nfec_block_batch* batch, const uint32_t* received,
+                      uint32_t mask_stride, const int32_t* status, uint32_t* stats, void* stream)
+{
+    int rc = check_object_call(codec, layout, object, batch, first_block);
+    if (rc) return rc;
+    if (received && (rc = check_mask(codec, received, mask_stride))) return rc;
+    if ((rc = check_batch(codec, batch)) || batch->nblocks == 0) return rc;
+    const nfec_codec* c = object_stripe(codec, object, batch);
+    if (!c) return NFEC_EINVAL;
+    DeviceGuard g(c->device);
+    ObjArgs a;
+    object_args(a, c, layout, object, object_bytes, first_block, batch);
+    a.received = received;
+    a.mask_stride = mask_stride;
+    a.status = status;
+    a.stats = stats;
+    return launch_obj_write(a, static_cast<hipStream_t>(stream));
+}
+
 // ---- per-call NORM semantics (synchronous, host vectors) ----
 // One call = gather the caller's vectors into the codec's pinned staging (host memcpy), one
 // H2D copy, the kernels, one D2H copy of what the call writes, one synchronize, scatter.  The

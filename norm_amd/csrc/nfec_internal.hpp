@@ -823,4 +823,30 @@ struct TxEmitArgs {
 };
 int launch_tx_emit(const TxEmitArgs& a, hipStream_t s);
 
+// Object segmentation on the device (kernels_obj.hip; nfec.h "object segmentation on the device").
+// One workgroup per run of up to 64 consecutive segments of a block; its lanes stride over the
+// run's (segment, 16-byte piece) pairs as one flat index.  Read: the object's bytes, at any
+// alignment, into the 8-byte aligned source slots, zero-padded to vec.  Write: the slots of the
+// selected segments back to their bytes of the object.
+struct ObjArgs {
+    uint8_t* base = nullptr;               // the batch
+    uint64_t block_stride = 0;
+    uint32_t seg_stride = 0;
+    uint32_t nblocks = 0;
+    uint32_t vec = 0;
+    uint8_t* object = nullptr;             // read: only read
+    uint64_t object_bytes = 0;
+    uint32_t first_block = 0;
+    nfec_object_layout lay{};
+    uint16_t* num_data_out = nullptr;      // read: [nblocks], or null
+    uint16_t* seg_length_out = nullptr;    // read: [nblocks][length_stride], or null
+    uint32_t length_stride = 0;
+    const uint32_t* received = nullptr;    // write: [nblocks][mask_stride], or null = every segment
+    uint32_t mask_stride = 0;
+    const int32_t* status = nullptr;       // write: [nblocks], or null
+    uint32_t* stats = nullptr;             // write: [2] selected, not selected (or null)
+};
+int launch_obj_read(const ObjArgs& a, hipStream_t s);
+int launch_obj_write(const ObjArgs& a, hipStream_t s);
+
 }  // namespace nfec

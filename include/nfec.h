@@ -25,6 +25,9 @@
  *   nfec_rx_place / nfec_decode_received
  *                         the segment copy, the reception mask and the erasure list of
  *                         NormObject::HandleObjectMessage  src/common/normObject.cpp:1548-1644
+ *   nfec_rx_ingest        the same with the FEC payload ID read from the message where it lies
+ *                         (NormPayloadId::GetFecBlockId / GetFecSymbolId / GetFecBlockLength,
+ *                         include/normMessage.h:485-544)
  *   nfec_tx_list / nfec_tx_emit
  *                         the pending walk, the payload lengths, the FEC payload ID and UnsetPending
  *                         of NormObject::NextSenderMsg  src/common/normObject.cpp:1877-2078
@@ -225,10 +228,12 @@ int nfec_decode(nfec_codec* codec, const nfec_block_batch* batch, const uint16_t
  * What NormObject::HandleObjectMessage does between a NORM_DATA arrival and the Decode call
  * (normObject.cpp:1548-1644) for a receiver whose segments are already in HBM: put each received
  * segment into its (block, slot) of a device batch, keep NORM's per-block reception mask, and
- * build the erasure lists Decode takes from that mask.  The wire layer (nfec_payload_id_read,
- * nfec_fti_read) gives (block, symbol) per segment on the host; only those descriptors are
- * uploaded.  All device entries are asynchronous on stream, like nfec_decode, and run on the
- * codec device that holds the batch (nfec_rx_erasures: the mask).
+ * build the erasure lists Decode takes from that mask.  Two ways in: nfec_rx_place takes (block,
+ * symbol) per segment as the wire layer (nfec_payload_id_read, nfec_fti_read) gives them on the
+ * host, and only those descriptors are uploaded; nfec_rx_ingest reads each message's FEC payload
+ * ID from the wire buffer on the device and needs no host-built descriptor.  All device entries are
+ * asynchronous on stream, like nfec_decode, and run on the codec device that holds the batch
+ * (nfec_rx_erasures: the mask).
  *
  * A reception mask is uint32_t received[nblocks][mask_stride] in device memory, mask_stride >=
  * (k + m + 31) / 32: bit s % 32 of word s / 32 is set when slot s of the block holds a received
@@ -255,6 +260,63 @@ typedef struct nfec_rx_segments {
  * rejected counts are added to stats[0..2].  batch->flags is ignored. */
 int nfec_rx_place(const nfec_codec* codec, const nfec_block_batch* batch, const nfec_rx_segments* segments,
                   uint32_t* received, uint32_t mask_stride, uint32_t* stats, void* stream);
+
+typedef struct nfec_rx_messages {      /* device arrays; offsets/length are nfec_tx_list's */
+    const void*     payloads;          /* the wire buffer, any byte alignment                   */
+    uint64_t        payload_bytes;     /* ... and its size                                      */
+    const uint64_t* offsets;           /* [count]: byte offset of message i's payload; its
+                                          payload ID is the idlen bytes in front of it          */
+    const uint16_t* length;            /* [count]: payload bytes                                */
+    uint32_t        count;
+    const uint64_t* count_dev;         /* device, may be NULL: process min(count, *count_dev)   */
+} nfec_rx_messages;
+
+/* The receiver intake, nfec_tx_emit's mirror: reads message i's FEC payload ID from the wire
+ * buffer and places its payload in the same pass.  With off = offsets[i], len = length[i] and
+ * idlen = nfec_payload_id_length(fec_id):
+ *   - NFEC_EINVAL for a fec_id / fec_m pair nfec_payload_id_read refuses, and for fec_id 0 (a
+ *     message without an ID names no slot).
+ *   - A message is unreadable when off < idlen or off + len > payload_bytes: it is rejected, its
+ *     outputs are 0xFFFFFFFF / 0xFFFF, and no byte of it is loaded.
+ *   - Otherwise the idlen bytes [off - idlen, off) are decoded exactly as nfec_payload_id_read
+ *     decodes them (big-endian, at any byte alignment) into block_id, s and, for fec_id 129,
+ *     block_len.  The block field has `bits` bits: 24 for fec_id 5 and fec_id 2 / fec_m 8, 16 for
+ *     fec_id 2 / fec_m 16, 32 for fec_id 129.  The block of the batch is b = (block_id -
+ *     first_block_id) mod 2^bits, the inverse of nfec_tx_emit's first_block_id + b after the ID's
+ *     truncation: a window that wraps the block field works.
+ *   - block_index_out[i] = b, even when b >= nblocks, and symbol_id_out[i] = s (device [count],
+ *     each may be NULL).
+ *   - From here on nfec_rx_place's rule with (b, s, len): rejected when b >= nblocks, nd_b is
+ *     outside [1, k], s >= nd_b + m or len > vector_size, and for fec_id 129 also when block_len !=
+ *     nd_b; otherwise the slot is claimed by one atomic OR on the reception mask, a duplicate is
+ *     dropped without a write, and a placed message's len bytes go into the slot, zeros up to
+ *     vector_size, nothing into [vector_size, seg_stride).
+ *   - stats[0..2] (device, may be NULL; the caller zeroes it) are nfec_rx_place's counters:
+ *     placed, duplicate, rejected.
+ *   - Every load from the wire buffer is an aligned chunk of at most 16 bytes that holds at least
+ *     one byte of [off - idlen, off + len), so no load leaves a page the message touches: the wire
+ *     buffer may end at the end of an allocation.  A duplicate or a rejected message loads its ID
+ *     chunk or chunks (two when the ID straddles a 16-byte boundary) and nothing else.
+ * With count_dev given, min(count, *count_dev) messages are processed and the outputs past them keep
+ * their bytes, so nfec_tx_list -> nfec_tx_emit -> nfec_rx_ingest chains on a stream: offsets and
+ * length are the list's arrays, count_dev its block_start + 2 * nblocks.  Asynchronous on stream,
+ * on the codec device that holds the batch; owns no codec state; batch->flags is ignored.  count ==
+ * 0 or nblocks == 0 is NFEC_OK and launches nothing; null and stride checks as nfec_rx_place. */
+int nfec_rx_ingest(const nfec_codec* codec, const nfec_block_batch* batch, const nfec_rx_messages* messages,
+                   uint8_t fec_id, uint8_t fec_m, uint32_t first_block_id,
+                   uint32_t* received, uint32_t mask_stride,
+                   uint32_t* block_index_out, uint16_t* symbol_id_out,   /* device [count], may be NULL */
+                   uint32_t* stats, void* stream);
+/* The parse half of nfec_rx_ingest's rule on host arrays (wire: wire_bytes bytes of host memory):
+ * no codec, no GPU.  For callers of the host-vector paths and of nfec_rx_place.  Fills
+ * block_index_out / symbol_id_out / block_len_out ([count], each may be NULL; block_len is 0 where
+ * the ID carries none); an unreadable message gets 0xFFFFFFFF / 0xFFFF / 0xFFFF.  Returns the number
+ * of readable messages; NFEC_EINVAL for a refused fec_id / fec_m pair or a null wire, offsets or
+ * length with count > 0, NFEC_ERANGE for a count above 2^31 - 1. */
+int nfec_rx_parse_host(uint8_t fec_id, uint8_t fec_m, uint32_t first_block_id,
+                       const void* wire, uint64_t wire_bytes, const uint64_t* offsets, const uint16_t* length,
+                       uint32_t count, uint32_t* block_index_out, uint16_t* symbol_id_out, uint16_t* block_len_out);
+
 /* The erasure lists nfec_decode takes, from reception masks, as NormObject builds them
  * (normObject.cpp:1560-1606): a block with no source slot of [0, nd_b) missing gets count 0 and
  * nothing listed (not even missing parity); otherwise every missing source slot ascending, then

@@ -10,7 +10,7 @@ from ._native import (NFEC_RS8, NFEC_RS16, NFEC_MDP, NFEC_ACCUMULATE, NFEC_FEATU
 from .codec import (  # noqa: F401
     NormEncoderRS8, NormDecoderRS8, NormEncoderRS16, NormDecoderRS16, NormEncoderMDP, NormDecoderMDP,
     BlockLayout, build_generator, device_count, fill_blocks, make_erasures, stream_copy, zero_erasures,
-    received_mask, erasures_from_received_host, tx_list_host, object_layout, object_segment, object_block_sizes,
+    received_mask, erasures_from_received_host, rx_parse_host, tx_list_host, object_layout, object_segment, object_block_sizes,
 )
 
 __version__ = "0.1.0"

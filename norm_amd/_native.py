@@ -60,6 +60,18 @@ class RxSegments(ctypes.Structure):
     ]
 
 
+class RxMessages(ctypes.Structure):
+    """nfec_rx_messages: the wire buffer and where each message's payload lies (device arrays)."""
+    _fields_ = [
+        ("payloads", ctypes.c_void_p),
+        ("payload_bytes", ctypes.c_uint64),
+        ("offsets", ctypes.c_void_p),
+        ("length", ctypes.c_void_p),
+        ("count", ctypes.c_uint32),
+        ("count_dev", ctypes.c_void_p),
+    ]
+
+
 class TxSegments(ctypes.Structure):
     """nfec_tx_segments: the wire buffer and the transmission list (device arrays)."""
     _fields_ = [
@@ -182,6 +194,9 @@ _SIGS = {
     "nfec_encode": (_I, [_P, ctypes.POINTER(BlockBatch), _P]),
     "nfec_decode": (_I, [_P, ctypes.POINTER(BlockBatch), _P, _U32, _P, _P, _P]),
     "nfec_rx_place": (_I, [_P, ctypes.POINTER(BlockBatch), ctypes.POINTER(RxSegments), _P, _U32, _P, _P]),
+    "nfec_rx_ingest": (_I, [_P, ctypes.POINTER(BlockBatch), ctypes.POINTER(RxMessages), _U8, _U8, _U32, _P, _U32, _P, _P,
+                            _P, _P]),
+    "nfec_rx_parse_host": (_I, [_U8, _U8, _U32, _P, _U64, _P, _P, _U32, _P, _P, _P]),
     "nfec_rx_erasures": (_I, [_P, _P, _U32, _P, _U32, _P, _U32, _P, _P]),
     "nfec_decode_received": (_I, [_P, ctypes.POINTER(BlockBatch), _P, _U32, _P, _P]),
     "nfec_rx_erasures_host": (_I, [_U32, _U32, _P, _U32, _P, _U32, _P, _U32, _P]),

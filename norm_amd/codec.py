@@ -236,6 +236,47 @@ class _Codec:
                                       received.shape[1], _tensor_ptr(stats, "stats"), _stream_handle(stream)),
                 "nfec_rx_place")
 
+    def ingest_messages(self, blocks, received, payloads, offsets, length, fec_id, fec_m=8, first_block_id=0,
+                        count_dev=None, num_data=None, block_index_out=None, symbol_id_out=None, stats=None,
+                        stream=None):
+        """place_segments with (block, slot) read on the device from the FEC payload ID in front of
+        each payload (nfec_rx_ingest).  payloads: the wire buffer, a uint8 tensor; offsets int64 /
+        length int16 per message, as list_pending returns them; fec_id / fec_m: the ID's form (5; 2
+        with 8 or 16; 129); first_block_id: the block ID of the batch's block 0.  count_dev: a
+        one-element int64 CUDA tensor (block_start[nblocks, :1]) that bounds the messages processed,
+        or None.  block_index_out int32 / symbol_id_out int16: tensors of one element per message
+        that receive what was parsed (all ones for a message outside the buffer), or None.  stats:
+        as place_segments."""
+        self._need()
+        b = _batch_struct(blocks, num_data, False)
+        _mask_check(received, blocks.shape[0])
+        count = offsets.numel()
+        given = [(offsets, 8, "offsets"), (length, 2, "length")]
+        given += [(t, size, what) for t, size, what in ((block_index_out, 4, "block_index_out"),
+                                                        (symbol_id_out, 2, "symbol_id_out")) if t is not None]
+        for t, size, what in given:
+            if t.element_size() != size or t.numel() != count:
+                raise ValueError(f"{what} must hold {count} elements of {size} bytes")
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous CUDA (HIP) tensor")
+        if stats is not None and (stats.element_size() != 4 or stats.numel() < 3):
+            raise ValueError("stats must hold three 32-bit counters")
+        if count_dev is not None and (count_dev.element_size() != 8 or count_dev.numel() < 1 or not count_dev.is_cuda):
+            raise ValueError("count_dev must be a 64-bit CUDA (HIP) tensor")
+        if payloads.element_size() != 1 or not payloads.is_cuda or not payloads.is_contiguous():
+            raise ValueError("payloads must be a contiguous uint8 CUDA (HIP) tensor")
+        msg = N.RxMessages()
+        msg.payloads = payloads.data_ptr() if payloads.numel() else None
+        msg.payload_bytes = payloads.numel()
+        msg.offsets, msg.length = offsets.data_ptr(), length.data_ptr()
+        msg.count = count
+        msg.count_dev = count_dev.data_ptr() if count_dev is not None else None
+        N.check(N.lib().nfec_rx_ingest(self._h, ctypes.byref(b), ctypes.byref(msg), fec_id, fec_m,
+                                       first_block_id & 0xFFFFFFFF, _tensor_ptr(received, "received"),
+                                       received.shape[1], _tensor_ptr(block_index_out, "block_index_out"),
+                                       _tensor_ptr(symbol_id_out, "symbol_id_out"), _tensor_ptr(stats, "stats"),
+                                       _stream_handle(stream)), "nfec_rx_ingest")
+
     def erasures_from_received(self, received, num_data=None, stride=None, stream=None):
         """The erasure lists decode_blocks takes, from a reception mask (nfec_rx_erasures):
         (locs int16 [nblocks, stride], counts int16 [nblocks]); stride defaults to numParity.
@@ -642,6 +683,28 @@ def erasures_from_received_host(k, m, received, num_data=None, stride=None):
     N.check(N.lib().nfec_rx_erasures_host(k, m, mask.ctypes.data, mask.shape[1], None if nd is None else nd.ctypes.data,
                                           nb, locs.ctypes.data, stride, counts.ctypes.data), "nfec_rx_erasures_host")
     return locs, counts
+
+
+def rx_parse_host(fec_id, fec_m, first_block_id, wire, offsets, length):
+    """nfec_rx_parse_host: what ingest_messages reads in front of each payload, on host arrays (no
+    GPU).  wire: NumPy uint8 array, the wire buffer; offsets 64-bit / length 16-bit arrays, one entry
+    per message.  Returns (block_index uint32, symbol_id uint16, block_len uint16): the block
+    relative to first_block_id inside the ID's block field, the slot, and fec_id 129's block length
+    (0 for the other forms); all ones for a message that does not lie inside the buffer."""
+    import numpy as np
+
+    wire = np.ascontiguousarray(wire).view(np.uint8).reshape(-1)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+    ln = np.ascontiguousarray(length, dtype=np.uint16).reshape(-1)
+    if off.size != ln.size:
+        raise ValueError("offsets and length must hold one entry per message")
+    block_index = np.zeros(off.size, np.uint32)
+    symbol_id = np.zeros(off.size, np.uint16)
+    block_len = np.zeros(off.size, np.uint16)
+    N.check(N.lib().nfec_rx_parse_host(fec_id, fec_m, first_block_id & 0xFFFFFFFF, wire.ctypes.data, wire.size,
+                                       off.ctypes.data, ln.ctypes.data, off.size, block_index.ctypes.data,
+                                       symbol_id.ctypes.data, block_len.ctypes.data), "nfec_rx_parse_host")
+    return block_index, symbol_id, block_len
 
 
 def tx_list_host(k, m, vector_size, pending, num_data=None, seg_length=None, gap=0, capacity=None):

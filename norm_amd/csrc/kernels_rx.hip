@@ -11,6 +11,7 @@
 #include <algorithm>
 
 #include "nfec_internal.hpp"
+#include "rx_parse.hpp"
 
 namespace nfec {
 
@@ -126,6 +127,132 @@ __global__ __launch_bounds__(256) void rx_place_kernel(RxPlaceArgs a)
     }
 }
 
+// ---- intake: (block, slot) from the FEC payload ID in front of the payload ----
+
+// The aligned 16-byte chunk that holds the ID's first byte and, when the ID straddles a chunk
+// boundary, the one after it.  Every lane reads the same address: one request per chunk.  Both
+// chunks hold an ID byte, so neither leaves a page the message touches.
+struct IdChunks {
+    u32x4 q0, q1;
+};
+__device__ __forceinline__ IdChunks load_id(const uint8_t* __restrict__ id, uint32_t idlen)
+{
+    const uint32_t res = (uint32_t)(reinterpret_cast<uintptr_t>(id) & 15u);
+    const u32x4* __restrict__ chunk = reinterpret_cast<const u32x4*>(id - res);
+    IdChunks c;
+    c.q0 = chunk[0];
+    c.q1 = u32x4{0u, 0u, 0u, 0u};
+    if (res + idlen > 16u) c.q1 = chunk[1];
+    return c;
+}
+
+// The ID's bytes 0-3 and 4-7 out of the chunks, as rx_id_decode takes them: the dword pick is a
+// uniform branch (res is wave-uniform), v_alignbyte_b32 funnels the bytes, and the result goes to
+// scalar registers.  A word past the ID's length may hold anything; rx_id_decode does not read it.
+__device__ __forceinline__ void id_words(const IdChunks& c, uint32_t res, uint32_t& w0, uint32_t& w1)
+{
+    const uint32_t dsh = res >> 2, bsh = res & 3u;
+    uint32_t e0, e1, e2;
+    switch (dsh) {
+    case 0: e0 = c.q0.x, e1 = c.q0.y, e2 = c.q0.z; break;
+    case 1: e0 = c.q0.y, e1 = c.q0.z, e2 = c.q0.w; break;
+    case 2: e0 = c.q0.z, e1 = c.q0.w, e2 = c.q1.x; break;
+    default: e0 = c.q0.w, e1 = c.q1.x, e2 = c.q1.y; break;
+    }
+    w0 = uniform(__builtin_amdgcn_alignbyte(e1, e0, bsh));
+    w1 = uniform(__builtin_amdgcn_alignbyte(e2, e1, bsh));
+}
+
+// rx_place_kernel's shape: one wave per message, four waves per workgroup, the workgroups striding
+// over the messages, the counters added once per wave.  A message needs three dependent fetches
+// before its copy (descriptor, ID, mask), so the wave runs them one message apart: message i + 1's
+// ID chunks and message i + 2's (offset, length) are requested ahead of message i's claim and
+// arrive with its answer, so a message costs the wave one round trip before its copy, as in
+// rx_place_kernel, and a duplicate costs that round trip alone.
+__global__ __launch_bounds__(256) void rx_ingest_kernel(RxIngestArgs a)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = uniform(blockIdx.x * 4u + (threadIdx.x >> 6));
+    const uint32_t nwaves = gridDim.x * 4u;
+    const uint32_t idlen = rx_id_length(a.id_kind);
+    uint64_t count = a.count;
+    if (a.count_dev) {
+        const uint64_t v = *a.count_dev;
+        const uint64_t have = ((uint64_t)uniform((uint32_t)(v >> 32)) << 32) | uniform((uint32_t)v);
+        count = min(count, have);
+    }
+    if (wave >= count) return;
+    uint32_t n_placed = 0, n_dup = 0, n_rej = 0;
+    // message `wave`: its descriptor and its ID; then the next one's descriptor
+    uint32_t v_len = a.length[wave];
+    uint64_t v_off = a.offsets[wave];
+    uint32_t len = uniform(v_len);
+    uint64_t off = ((uint64_t)uniform((uint32_t)(v_off >> 32)) << 32) | uniform((uint32_t)v_off);
+    bool readable = rx_readable(off, len, idlen, a.payload_bytes);
+    IdChunks id{};
+    if (readable) id = load_id(a.payloads + (off - idlen), idlen);
+    if ((uint64_t)wave + nwaves < count) v_len = a.length[wave + nwaves], v_off = a.offsets[wave + nwaves];
+    for (uint64_t i = wave; i < count; i += nwaves) {
+        // message i + nwaves: its descriptor is here (requested an iteration ago, ahead of that
+        // message's claim, whose round trip it shared); request its ID and the descriptor of the
+        // message after it now, ahead of this message's claim
+        const uint64_t nxt = i + nwaves;
+        uint32_t n_len = 0;
+        uint64_t n_off = 0;
+        bool n_readable = false;
+        IdChunks n_id{};
+        if (nxt < count) {
+            n_len = uniform(v_len);
+            n_off = ((uint64_t)uniform((uint32_t)(v_off >> 32)) << 32) | uniform((uint32_t)v_off);
+            n_readable = rx_readable(n_off, n_len, idlen, a.payload_bytes);
+            if (n_readable) n_id = load_id(a.payloads + (n_off - idlen), idlen);
+            if (nxt + nwaves < count) v_len = a.length[nxt + nwaves], v_off = a.offsets[nxt + nwaves];
+        }
+        // parse and claim message i: its ID was requested an iteration ago
+        uint32_t b = 0xffffffffu, s = 0xffffu;
+        bool place = false;
+        if (readable) {
+            uint32_t w0, w1;
+            id_words(id, (uint32_t)(reinterpret_cast<uintptr_t>(a.payloads + (off - idlen)) & 15u), w0, w1);
+            const RxId pid = rx_id_decode(a.id_kind, w0, w1, a.first_block_id);
+            b = pid.block, s = pid.symbol;
+            bool ok = b < a.nblocks && len <= a.vec;
+            if (ok) {
+                const uint32_t nd = a.num_data ? uniform(a.num_data[b]) : a.k;
+                ok = nd >= 1 && nd <= a.k && s < nd + a.m && (a.id_kind != RX_ID_BLOCK32_LEN || pid.block_len == nd);
+            }
+            if (ok) {
+                // lane 0 claims the slot; the outcome goes to the whole wave
+                uint32_t was = 0;
+                if (lane == 0) {
+                    const uint32_t bit = 1u << (s & 31u);
+                    was = atomicOr(a.received + (uint64_t)b * a.mask_stride + (s >> 5), bit) & bit;
+                }
+                was = __builtin_amdgcn_readlane(was, 0);
+                if (was) ++n_dup;
+                else ++n_placed, place = true;
+            } else {
+                ++n_rej;
+            }
+        } else {
+            ++n_rej;
+        }
+        if (lane == 0) {
+            if (a.block_index_out) a.block_index_out[i] = b;
+            if (a.symbol_id_out) a.symbol_id_out[i] = (uint16_t)s;
+        }
+        if (place)
+            place_segment(a.base + (uint64_t)b * a.block_stride + (uint64_t)s * a.seg_stride, a.payloads + off, len,
+                          a.vec, lane);
+        len = n_len, off = n_off, readable = n_readable, id = n_id;
+    }
+    if (a.stats && lane == 0) {
+        if (n_placed) atomicAdd(a.stats + 0, n_placed);
+        if (n_dup) atomicAdd(a.stats + 1, n_dup);
+        if (n_rej) atomicAdd(a.stats + 2, n_rej);
+    }
+}
+
 // exclusive prefix sum of v over the wave's 64 lanes; total: the sum over all of them
 __device__ __forceinline__ uint32_t wave_scan(uint32_t v, uint32_t lane, uint32_t& total)
 {
@@ -211,6 +338,29 @@ int launch_rx_place(const RxPlaceArgs& a, hipStream_t s)
     hipLaunchKernelGGL(rx_place_kernel, dim3(grid), dim3(256), 0, s, a);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? NFEC_OK : hip_fail(e, "rx_place launch");
+}
+
+int launch_rx_ingest(const RxIngestArgs& a, hipStream_t s)
+{
+    if (a.count == 0 || a.nblocks == 0) return NFEC_OK;
+    if (a.id_kind != RX_ID_BLOCK24 && a.id_kind != RX_ID_BLOCK16 && a.id_kind != RX_ID_BLOCK32_LEN)
+        return fail(NFEC_EINVAL, "rx_ingest: bad fec_id / fec_m");
+    if (!a.base) return fail(NFEC_EINVAL, "rx_ingest: null blocks pointer");
+    if (!a.payloads) return fail(NFEC_EINVAL, "rx_ingest: null payloads");
+    if (!a.offsets) return fail(NFEC_EINVAL, "rx_ingest: null offsets");
+    if (!a.length) return fail(NFEC_EINVAL, "rx_ingest: null length");
+    if (!a.received) return fail(NFEC_EINVAL, "rx_ingest: null received mask");
+    if ((uint64_t)a.mask_stride * 32u < (uint64_t)a.k + a.m)
+        return fail(NFEC_EINVAL, "rx_ingest: mask_stride smaller than (k + m + 31) / 32");
+    if ((reinterpret_cast<uintptr_t>(a.base) | a.block_stride | a.seg_stride) & 7)
+        return fail(NFEC_EINVAL, "rx_ingest: blocks, seg_stride and block_stride must be multiples of 8 bytes");
+    if (a.seg_stride < a.vec) return fail(NFEC_EINVAL, "rx_ingest: seg_stride < vector_size");
+    // the grid of rx_place
+    constexpr uint32_t kMaxGroups = 8192;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)a.count + 3u) / 4u, kMaxGroups);
+    hipLaunchKernelGGL(rx_ingest_kernel, dim3(grid), dim3(256), 0, s, a);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? NFEC_OK : hip_fail(e, "rx_ingest launch");
 }
 
 int launch_rx_erasures(const RxErasureArgs& a, hipStream_t s)

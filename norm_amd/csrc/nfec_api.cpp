@@ -22,6 +22,7 @@
 
 #include "bitslice.hpp"
 #include "codec_state.hpp"
+#include "rx_parse.hpp"
 
 using namespace nfec;
 
@@ -724,6 +725,48 @@ int nfec_rx_place(const nfec_codec* codec, const nfec_block_batch* batch, const 
     a.mask_stride = mask_stride;
     a.stats = stats;
     return launch_rx_place(a, static_cast<hipStream_t>(stream));
+}
+
+int nfec_rx_ingest(const nfec_codec* codec, const nfec_block_batch* batch, const nfec_rx_messages* msg, uint8_t fec_id,
+                   uint8_t fec_m, uint32_t first_block_id, uint32_t* received, uint32_t mask_stride,
+                   uint32_t* block_index_out, uint16_t* symbol_id_out, uint32_t* stats, void* stream)
+{
+    if (!codec || !batch || !msg) return fail(NFEC_EINVAL, "null codec, batch or messages");
+    int rc = check_mask(codec, received, mask_stride);
+    if (rc) return rc;
+    if (msg->count && !msg->payloads) return fail(NFEC_EINVAL, "null messages->payloads");
+    if (msg->count && !msg->offsets) return fail(NFEC_EINVAL, "null messages->offsets");
+    if (msg->count && !msg->length) return fail(NFEC_EINVAL, "null messages->length");
+    const uint32_t id_kind = rx_id_kind(fec_id, fec_m);
+    if (id_kind == RX_ID_REFUSED) return fail(NFEC_EINVAL, "bad fec_id / fec_m");
+    if ((rc = check_batch(codec, batch)) || batch->nblocks == 0 || msg->count == 0) return rc;
+    // (the stripe is only read: its shape and its device)
+    const nfec_codec* c = stripe_for(const_cast<nfec_codec*>(codec), batch->blocks);
+    if (!c) return fail(NFEC_EINVAL, "batch is not on a device of the codec");
+    DeviceGuard g(c->device);
+    RxIngestArgs a;
+    a.base = static_cast<uint8_t*>(batch->blocks);
+    a.block_stride = batch->block_stride;
+    a.seg_stride = batch->seg_stride;
+    a.nblocks = batch->nblocks;
+    a.num_data = batch->num_data;
+    a.k = c->k;
+    a.m = c->m;
+    a.vec = c->vec;
+    a.payloads = static_cast<const uint8_t*>(msg->payloads);
+    a.payload_bytes = msg->payload_bytes;
+    a.offsets = msg->offsets;
+    a.length = msg->length;
+    a.count = msg->count;
+    a.count_dev = msg->count_dev;
+    a.id_kind = id_kind;
+    a.first_block_id = first_block_id;
+    a.received = received;
+    a.mask_stride = mask_stride;
+    a.block_index_out = block_index_out;
+    a.symbol_id_out = symbol_id_out;
+    a.stats = stats;
+    return launch_rx_ingest(a, static_cast<hipStream_t>(stream));
 }
 
 int nfec_rx_erasures(const nfec_codec* codec, const uint32_t* received, uint32_t mask_stride, const uint16_t* num_data,

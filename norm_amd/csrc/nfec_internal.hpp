@@ -763,6 +763,30 @@ struct RxPlaceArgs {
     uint32_t* stats = nullptr;           // [3] placed, duplicate, rejected (or null)
 };
 int launch_rx_place(const RxPlaceArgs& a, hipStream_t s);
+// Intake: place with (block, slot) read from the FEC payload ID in front of each payload in the
+// wire buffer (rx_parse.hpp holds the rule); one wave per message, as place.
+struct RxIngestArgs {
+    uint8_t* base = nullptr;             // the batch
+    uint64_t block_stride = 0;
+    uint32_t seg_stride = 0;
+    uint32_t nblocks = 0;
+    const uint16_t* num_data = nullptr;  // per block, or null = k
+    uint32_t k = 0, m = 0, vec = 0;
+    const uint8_t* payloads = nullptr;   // the wire buffer
+    uint64_t payload_bytes = 0;
+    const uint64_t* offsets = nullptr;
+    const uint16_t* length = nullptr;
+    uint32_t count = 0;
+    const uint64_t* count_dev = nullptr; // device, or null: min(count, *count_dev) messages
+    uint32_t id_kind = 0;                // the payload ID's layout (RX_ID_*, rx_parse.hpp)
+    uint32_t first_block_id = 0;
+    uint32_t* received = nullptr;        // [nblocks][mask_stride]
+    uint32_t mask_stride = 0;
+    uint32_t* block_index_out = nullptr; // [count], or null
+    uint16_t* symbol_id_out = nullptr;   // [count], or null
+    uint32_t* stats = nullptr;           // [3] placed, duplicate, rejected (or null)
+};
+int launch_rx_ingest(const RxIngestArgs& a, hipStream_t s);
 // Erasure lists from reception masks: one wave per block, lanes over mask words.
 struct RxErasureArgs {
     const uint32_t* received = nullptr;

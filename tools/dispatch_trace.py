@@ -17,6 +17,9 @@ The host_* cases run a host-resident batch (nfec_*_host, nfec_*_host_vectors) in
 of 4 blocks: three chunks, one per slot, the last ragged; the 13-block case reuses a slot.
 Trace them with `--kernel-trace --memory-copy-trace --output-format csv json`: `join` then also
 gives the multiset of copies, [direction, bytes, how many] (the JSON output carries the sizes).
+
+The rx_ingest case runs encode, nfec_tx_list and nfec_tx_emit into a wire buffer and then the
+receiver intake, nfec_rx_ingest, on that buffer.
 """
 import csv
 import glob
@@ -73,6 +76,8 @@ CASES = {
     "host_dec_mdp_24_8_v600_pageable": ("dec", "MDP", 24, 8, 600, {"host": "pageable", "erase": 8}),
     "host_enc_rs16_30_10_v998_pinned": ("enc", "RS16", 30, 10, 998, {"host": "pinned", "stride": 1000}),
     "host_dec_rs8_13_blocks_pinned": ("dec", "RS8", 64, 32, 1400, {"host": "pinned", "nb": 13}),
+    # receiver intake: encode, list, emit, then nfec_rx_ingest of the wire buffer into a second batch
+    "rx_ingest_rs8_64_32_v1400": ("ingest", "RS8", 64, 32, 1400, {}),
 }
 
 
@@ -117,6 +122,14 @@ def run(name):
         _host_call(enc, call, how, blocks, nd, kw.get("acc", False))
     elif call == "enc":
         enc.encode_blocks(blocks, num_data=nd, accumulate=kw.get("acc", False))
+    elif call == "ingest":
+        enc.encode_blocks(blocks, num_data=nd)
+        pending = torch.full((nb, (k + m + 31) // 32), -1, dtype=torch.int32, device="cuda")
+        off, blk, sym, ln, start = enc.list_pending(pending, num_data=nd, gap=13)
+        wire = torch.zeros(nb * (k + m) * (13 + vec), dtype=torch.uint8, device="cuda")
+        enc.emit_segments(blocks, wire, off, blk, sym, ln, count_dev=start[nb, :1], fec_id=5, num_data=nd)
+        enc.ingest_messages(torch.zeros_like(blocks), C.received_mask(nb, k, m), wire, off, ln, 5,
+                            count_dev=start[nb, :1], num_data=nd)
     else:
         enc.encode_blocks(blocks, num_data=nd)
         codec = getattr(C, "NormDecoder" + kind)(options=opts)

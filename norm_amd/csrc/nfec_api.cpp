@@ -682,6 +682,20 @@ int nfec_decode(nfec_codec* codec, const nfec_block_batch* batch, const uint16_t
 // ---- receiver assembly on the device (kernels_rx.hip) ----
 // Arguments are checked before the codec's device is: a null array or a short mask is
 // NFEC_EINVAL on any codec, a host-only codec answers NFEC_EDEVICE to well-formed calls.
+static BatchView batch_view(const nfec_codec* c, const nfec_block_batch* batch)
+{
+    BatchView v;
+    v.base = static_cast<uint8_t*>(batch->blocks);
+    v.block_stride = batch->block_stride;
+    v.seg_stride = batch->seg_stride;
+    v.nblocks = batch->nblocks;
+    v.num_data = batch->num_data;
+    v.k = c->k;
+    v.m = c->m;
+    v.vec = c->vec;
+    return v;
+}
+
 static int check_mask(const nfec_codec* c, const uint32_t* received, uint32_t mask_stride)
 {
     if (!received) return fail(NFEC_EINVAL, "null received mask");
@@ -707,14 +721,7 @@ int nfec_rx_place(const nfec_codec* codec, const nfec_block_batch* batch, const 
     if (!c) return fail(NFEC_EINVAL, "batch is not on a device of the codec");
     DeviceGuard g(c->device);
     RxPlaceArgs a;
-    a.base = static_cast<uint8_t*>(batch->blocks);
-    a.block_stride = batch->block_stride;
-    a.seg_stride = batch->seg_stride;
-    a.nblocks = batch->nblocks;
-    a.num_data = batch->num_data;
-    a.k = c->k;
-    a.m = c->m;
-    a.vec = c->vec;
+    a.batch = batch_view(c, batch);
     a.payloads = static_cast<const uint8_t*>(seg->payloads);
     a.offsets = seg->offsets;
     a.block_index = seg->block_index;
@@ -737,22 +744,15 @@ int nfec_rx_ingest(const nfec_codec* codec, const nfec_block_batch* batch, const
     if (msg->count && !msg->payloads) return fail(NFEC_EINVAL, "null messages->payloads");
     if (msg->count && !msg->offsets) return fail(NFEC_EINVAL, "null messages->offsets");
     if (msg->count && !msg->length) return fail(NFEC_EINVAL, "null messages->length");
-    const uint32_t id_kind = rx_id_kind(fec_id, fec_m);
-    if (id_kind == RX_ID_REFUSED) return fail(NFEC_EINVAL, "bad fec_id / fec_m");
+    const uint32_t id_kind = payload_id_kind(fec_id, fec_m);
+    if (id_kind == PAYLOAD_ID_NONE) return fail(NFEC_EINVAL, "bad fec_id / fec_m");
     if ((rc = check_batch(codec, batch)) || batch->nblocks == 0 || msg->count == 0) return rc;
     // (the stripe is only read: its shape and its device)
     const nfec_codec* c = stripe_for(const_cast<nfec_codec*>(codec), batch->blocks);
     if (!c) return fail(NFEC_EINVAL, "batch is not on a device of the codec");
     DeviceGuard g(c->device);
     RxIngestArgs a;
-    a.base = static_cast<uint8_t*>(batch->blocks);
-    a.block_stride = batch->block_stride;
-    a.seg_stride = batch->seg_stride;
-    a.nblocks = batch->nblocks;
-    a.num_data = batch->num_data;
-    a.k = c->k;
-    a.m = c->m;
-    a.vec = c->vec;
+    a.batch = batch_view(c, batch);
     a.payloads = static_cast<const uint8_t*>(msg->payloads);
     a.payload_bytes = msg->payload_bytes;
     a.offsets = msg->offsets;
@@ -878,25 +878,15 @@ int nfec_tx_emit(const nfec_codec* codec, const nfec_block_batch* batch, const n
     if (seg->count && !seg->block_index) return fail(NFEC_EINVAL, "null segments->block_index");
     if (seg->count && !seg->symbol_id) return fail(NFEC_EINVAL, "null segments->symbol_id");
     if (seg->count && !seg->length) return fail(NFEC_EINVAL, "null segments->length");
-    uint32_t id_kind = TX_ID_NONE;
-    if (fec_id) {
-        uint8_t probe[8];
-        if (nfec_payload_id_write(fec_id, fec_m, 0, 0, 0, probe) < 0) return fail(NFEC_EINVAL, "bad fec_id / fec_m");
-        id_kind = fec_id == 129 ? TX_ID_BLOCK32_LEN : fec_id == 2 && fec_m == 16 ? TX_ID_BLOCK16 : TX_ID_BLOCK24;
-    }
+    // fec_id 0: no ID in front of the payloads
+    const uint32_t id_kind = fec_id ? payload_id_kind(fec_id, fec_m) : (uint32_t)PAYLOAD_ID_NONE;
+    if (fec_id && id_kind == PAYLOAD_ID_NONE) return fail(NFEC_EINVAL, "bad fec_id / fec_m");
     if ((rc = check_batch(codec, batch)) || batch->nblocks == 0 || seg->count == 0) return rc;
     const nfec_codec* c = stripe_for(const_cast<nfec_codec*>(codec), batch->blocks);
     if (!c) return fail(NFEC_EINVAL, "batch is not on a device of the codec");
     DeviceGuard g(c->device);
     TxEmitArgs a;
-    a.base = static_cast<const uint8_t*>(batch->blocks);
-    a.block_stride = batch->block_stride;
-    a.seg_stride = batch->seg_stride;
-    a.nblocks = batch->nblocks;
-    a.num_data = batch->num_data;
-    a.k = c->k;
-    a.m = c->m;
-    a.vec = c->vec;
+    a.batch = batch_view(c, batch);
     a.payloads = static_cast<uint8_t*>(seg->payloads);
     a.payload_bytes = seg->payload_bytes;
     a.offsets = seg->offsets;
@@ -962,11 +952,7 @@ static const nfec_codec* object_stripe(const nfec_codec* codec, const void* obje
 static void object_args(ObjArgs& a, const nfec_codec* c, const nfec_object_layout* layout, const void* object,
                         uint64_t object_bytes, uint32_t first_block, const nfec_block_batch* batch)
 {
-    a.base = static_cast<uint8_t*>(batch->blocks);
-    a.block_stride = batch->block_stride;
-    a.seg_stride = batch->seg_stride;
-    a.nblocks = batch->nblocks;
-    a.vec = c->vec;
+    a.batch = batch_view(c, batch);
     a.object = static_cast<uint8_t*>(const_cast<void*>(object));
     a.object_bytes = object_bytes;
     a.first_block = first_block;

@@ -742,16 +742,24 @@ struct ErasureListArgs {
 };
 int launch_erasure_list(const ErasureListArgs& a, hipStream_t s);
 
+// A device batch as the tx, rx and object kernels see it: the caller's nfec_block_batch (checked by
+// check_batch) and the codec's shape.  nfec_api.cpp fills it (batch_view).  The launchers of these
+// kernels check nothing: the ABI entry has refused every malformed call, with its own message,
+// and has returned for an empty batch or list.
+struct BatchView {
+    uint8_t* base = nullptr;             // the batch (8-byte aligned, as both strides are)
+    uint64_t block_stride = 0;
+    uint32_t seg_stride = 0;             // >= vec
+    uint32_t nblocks = 0;
+    const uint16_t* num_data = nullptr;  // per block, or null = k
+    uint32_t k = 0, m = 0, vec = 0;
+};
+
 // Receiver assembly on the device (kernels_rx.hip; nfec.h "receiver assembly on the device").
 // Place: one wave per segment; lane 0 claims the slot's mask bit, the wave then copies the
 // payload from any byte alignment into the 8-byte aligned slot and zero-pads it to vec.
 struct RxPlaceArgs {
-    uint8_t* base = nullptr;             // the batch
-    uint64_t block_stride = 0;
-    uint32_t seg_stride = 0;
-    uint32_t nblocks = 0;
-    const uint16_t* num_data = nullptr;  // per block, or null = k
-    uint32_t k = 0, m = 0, vec = 0;
+    BatchView batch;
     const uint8_t* payloads = nullptr;
     const uint64_t* offsets = nullptr;
     const uint32_t* block_index = nullptr;
@@ -766,19 +774,14 @@ int launch_rx_place(const RxPlaceArgs& a, hipStream_t s);
 // Intake: place with (block, slot) read from the FEC payload ID in front of each payload in the
 // wire buffer (rx_parse.hpp holds the rule); one wave per message, as place.
 struct RxIngestArgs {
-    uint8_t* base = nullptr;             // the batch
-    uint64_t block_stride = 0;
-    uint32_t seg_stride = 0;
-    uint32_t nblocks = 0;
-    const uint16_t* num_data = nullptr;  // per block, or null = k
-    uint32_t k = 0, m = 0, vec = 0;
+    BatchView batch;
     const uint8_t* payloads = nullptr;   // the wire buffer
     uint64_t payload_bytes = 0;
     const uint64_t* offsets = nullptr;
     const uint16_t* length = nullptr;
     uint32_t count = 0;
     const uint64_t* count_dev = nullptr; // device, or null: min(count, *count_dev) messages
-    uint32_t id_kind = 0;                // the payload ID's layout (RX_ID_*, rx_parse.hpp)
+    uint32_t id_kind = 0;                // the payload ID's layout (PAYLOAD_ID_*, rx_parse.hpp)
     uint32_t first_block_id = 0;
     uint32_t* received = nullptr;        // [nblocks][mask_stride]
     uint32_t mask_stride = 0;
@@ -823,14 +826,8 @@ struct TxListArgs {
 int launch_tx_list(const TxListArgs& a, hipStream_t s);
 // Emit: one wave per entry; the 8-byte aligned slot goes to any byte offset of the wire buffer
 // behind its FEC payload ID, and lane 0 clears the slot's pending bit.
-enum { TX_ID_NONE = 0, TX_ID_BLOCK24 = 1, TX_ID_BLOCK16 = 2, TX_ID_BLOCK32_LEN = 3 };
 struct TxEmitArgs {
-    const uint8_t* base = nullptr;         // the batch
-    uint64_t block_stride = 0;
-    uint32_t seg_stride = 0;
-    uint32_t nblocks = 0;
-    const uint16_t* num_data = nullptr;    // per block, or null = k
-    uint32_t k = 0, m = 0, vec = 0;
+    BatchView batch;                       // (only read)
     uint8_t* payloads = nullptr;           // the wire buffer
     uint64_t payload_bytes = 0;
     const uint64_t* offsets = nullptr;
@@ -839,7 +836,7 @@ struct TxEmitArgs {
     const uint16_t* length = nullptr;
     uint32_t count = 0;
     const uint64_t* count_dev = nullptr;   // device, or null: min(count, *count_dev) entries
-    uint32_t id_kind = TX_ID_NONE;         // the payload ID's layout (TX_ID_*)
+    uint32_t id_kind = 0;                  // the payload ID's layout (PAYLOAD_ID_*, rx_parse.hpp)
     uint32_t first_block_id = 0;
     uint32_t* pending = nullptr;           // [nblocks][mask_stride], or null
     uint32_t mask_stride = 0;
@@ -853,11 +850,7 @@ int launch_tx_emit(const TxEmitArgs& a, hipStream_t s);
 // alignment, into the 8-byte aligned source slots, zero-padded to vec.  Write: the slots of the
 // selected segments back to their bytes of the object.
 struct ObjArgs {
-    uint8_t* base = nullptr;               // the batch
-    uint64_t block_stride = 0;
-    uint32_t seg_stride = 0;
-    uint32_t nblocks = 0;
-    uint32_t vec = 0;
+    BatchView batch;
     uint8_t* object = nullptr;             // read: only read
     uint64_t object_bytes = 0;
     uint32_t first_block = 0;

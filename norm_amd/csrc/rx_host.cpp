@@ -58,15 +58,15 @@ extern "C" int nfec_rx_parse_host(uint8_t fec_id, uint8_t fec_m, uint32_t first_
                                   uint64_t wire_bytes, const uint64_t* offsets, const uint16_t* length, uint32_t count,
                                   uint32_t* block_index_out, uint16_t* symbol_id_out, uint16_t* block_len_out)
 {
-    const uint32_t kind = rx_id_kind(fec_id, fec_m);
-    if (kind == RX_ID_REFUSED) return fail(NFEC_EINVAL, "rx_parse_host: bad fec_id / fec_m");
+    const uint32_t kind = payload_id_kind(fec_id, fec_m);
+    if (kind == PAYLOAD_ID_NONE) return fail(NFEC_EINVAL, "rx_parse_host: bad fec_id / fec_m");
     if (count == 0) return 0;
     if (count > 0x7fffffffu) return fail(NFEC_ERANGE, "rx_parse_host: count above 2^31 - 1");
     if (!wire) return fail(NFEC_EINVAL, "rx_parse_host: null wire");
     if (!offsets) return fail(NFEC_EINVAL, "rx_parse_host: null offsets");
     if (!length) return fail(NFEC_EINVAL, "rx_parse_host: null length");
     const uint8_t* bytes = static_cast<const uint8_t*>(wire);
-    const uint32_t idlen = rx_id_length(kind);
+    const uint32_t idlen = payload_id_length(kind);
     int readable = 0;
     for (uint32_t i = 0; i < count; ++i) {
         RxId id{0xffffffffu, 0xffffu, 0xffffu};

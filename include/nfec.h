@@ -34,6 +34,9 @@
  *   nfec_object_layout_for / nfec_object_read / nfec_object_write
  *                         the block partition of NormObject::Open  src/common/normObject.cpp:134-137,
  *                         :203-231, NormDataObject::ReadSegment :2673-2718 and WriteSegment :2628-2670
+ *   nfec_stream_frame / nfec_stream_pack / nfec_stream_unpack
+ *                         NormStreamObject::Write  src/common/normObject.cpp:4039-4232, the stream
+ *                         payload header include/normMessage.h:1145-1196, ReadPrivate :3700-3860
  *   nfec_encode_host_vectors / nfec_decode_host_vectors
  *                         the same two sites on NORM's scattered segment lists (block->SegmentList())
  *   nfec_encode_segment   NormEncoder::Encode(segmentId, dataVector, parityVectorList)
@@ -420,7 +423,8 @@ int nfec_tx_emit(const nfec_codec* codec, const nfec_block_batch* batch, const n
  * blocks), NormDataObject::ReadSegment (:2673-2718) with the zero pad of CalculateBlockParity
  * (:2203-2229) on the sender, and NormDataObject::WriteSegment (:2628-2670) on the receiver, which
  * is called for every received source segment (:1529) and for every repaired one after a
- * successful Decode (:1616).  Non-stream objects only: the entries take no object type.
+ * successful Decode (:1616).  Non-stream objects only: the entries take no object type
+ * (NORM_OBJECT_STREAM has the next section's).
  *
  * The partition.  num_segments = ceil(object_size / segment_size) and num_blocks =
  * ceil(num_segments / num_data) (NormObjectSize's divide rounds up everywhere); large_block_size =
@@ -503,6 +507,140 @@ int nfec_object_write(const nfec_codec* codec, const nfec_object_layout* layout,
                       uint64_t object_bytes, uint32_t first_block, const nfec_block_batch* batch,
                       const uint32_t* received, uint32_t mask_stride, const int32_t* status,
                       uint32_t* stats, void* stream);
+
+/* ---- stream objects on the device ----
+ * NORM's third object kind, NORM_OBJECT_STREAM: the reason every codec has vector_size =
+ * segment_size + 8.  A stream segment is the 8-byte stream payload header (include/normMessage.h:
+ * 1145-1196: payload_len, 2 bytes big-endian, at byte 0; payload_msg_start, 2 BE, at 2;
+ * payload_offset, 4 BE, at 4) and up to segment_size bytes of the stream from byte 8 on.  The
+ * three steps of NormStreamObject for a caller whose stream bytes are in HBM: frame (which bytes
+ * make which segment: NormStreamObject::Write, src/common/normObject.cpp:4039-4232, the loop body
+ * :4166-4210), pack (the segments into the source slots of a batch, one step before nfec_encode)
+ * and unpack (repaired blocks back to the byte stream, one step after nfec_decode_received; what
+ * NormStreamObject::ReadPrivate, :3700-3860, reads out of its segments).
+ *
+ * The framing rule.  A call frames n application writes (write_len[i], write_flags[i]) that lie
+ * one behind the other in the stream; NFEC_STREAM_EOM: the write ends a message (Write's eom),
+ * NFEC_STREAM_FLUSH: the flush mode of the write was not FLUSH_NONE.  The call's byte run is the
+ * carry -- the state's carry_bytes bytes of the open trailing segment the calls before left --
+ * followed by the writes; position 0 is its first byte, S = segment_size.  Cuts: position 0 and
+ * the end position of every FLUSH write (coinciding cuts are one).  Between consecutive cuts a < b
+ * lie ceil((b - a) / S) segments, segment j being [a + j S, min(a + (j + 1) S, b)); behind the
+ * last cut only the full segments are closed, the rest (fewer than S bytes) is the new carry and
+ * is not emitted.  No empty segment is emitted (:4198-4199: a flush closes a segment only when it
+ * holds a byte).  A write is a message start when its length is not 0 and it is the stream's
+ * first such write (:2788, msg_start(true)) or an EOM write lies between the nonzero write before
+ * it and it, that write included (:4175-4180, :4214-4217: a zero-length EOM write raises the flag
+ * too, and a zero-length write never takes it).  The header of segment [s, e): payload_len = e -
+ * s; payload_msg_start = p - s + 1 for the first message-start position p in [s, e), else 0;
+ * payload_offset = write_offset + s (mod 2^32), write_offset being the stream offset of position
+ * 0.  Segment i of a call goes to slot q = first_slot + i of the stream: block q / k, slot q % k of
+ * a batch whose block 0 is the block of slot 0 (stream blocks are always k wide, :2779). */
+#define NFEC_STREAM_EOM   1u   /* write_flags: the write ends a message                         */
+#define NFEC_STREAM_FLUSH 2u   /* write_flags: flush mode other than FLUSH_NONE                 */
+#define NFEC_STREAM_END   1u   /* nfec_stream_pack flags: append Terminate's control segment    */
+
+typedef struct nfec_stream_state {     /* a fresh stream: {0, 1, 0, 0, 0} (:2788, :2798)        */
+    uint32_t write_offset;       /* stream offset of the carry's first byte; wraps at 2^32      */
+    uint32_t msg_start_pending;  /* Write's msg_start flag: the next nonzero write starts a message */
+    uint32_t carry_bytes;        /* bytes of the open trailing segment, < segment_size          */
+    uint32_t carry_msg_start;    /* 0, or 1 + the position of the carry's first message start   */
+    uint64_t next_slot;          /* segments closed so far: the next call's first_slot          */
+} nfec_stream_state;
+
+/* The rule on host arrays: no codec, no GPU.  seg_start[i] (byte offset of segment i's first byte
+ * in the call's byte run, the carry included), seg_len[i] and seg_msg_start[i] hold `capacity`
+ * entries; totals[4] = {segments, bytes consumed (the position at which the new carry begins: the
+ * next call's byte run starts there), carry bytes, carry_msg_start}.  The totals are the full
+ * numbers even past capacity; only the first `capacity` entries are written (nfec_tx_list's
+ * rule).  *state is advanced (write_offset by the bytes consumed, next_slot by the segments), so
+ * that framing the same writes in one call, or split over several calls at any write boundary,
+ * gives the same segments.  NFEC_EINVAL for a null state or totals, null write arrays with n > 0,
+ * null output arrays with capacity > 0, a segment_size outside [1, 65535 - 8], or a state with
+ * carry_bytes >= segment_size or carry_msg_start > carry_bytes. */
+int nfec_stream_frame_host(uint32_t segment_size, const uint32_t* write_len, const uint8_t* write_flags,
+                           uint32_t n, nfec_stream_state* state, uint64_t* seg_start, uint16_t* seg_len,
+                           uint16_t* seg_msg_start, uint32_t capacity, uint64_t* totals);
+
+/* The same on device arrays, asynchronously on stream, on the codec device that holds totals; it
+ * owns no codec state.  The state comes by value; the advanced state is written to *state_out
+ * (device) and totals is a device uint64[4], so nfec_stream_pack (count_dev = totals) and the
+ * caller's next step chain on them without a synchronize.  workspace: device, 8-byte aligned,
+ * NFEC_STREAM_FRAME_WORKSPACE(n, capacity) bytes, the call's only workspace (five 64-bit words
+ * per write: its scans).  Errors as the host entry's, plus a null workspace or state_out. */
+#define NFEC_STREAM_FRAME_WORKSPACE(n, capacity) (((uint64_t)(n) + 2u) * 40u)
+int nfec_stream_frame(const nfec_codec* codec, uint32_t segment_size, const uint32_t* write_len,
+                      const uint8_t* write_flags, uint32_t n, nfec_stream_state state,
+                      nfec_stream_state* state_out, uint64_t* seg_start, uint16_t* seg_len,
+                      uint16_t* seg_msg_start, uint32_t capacity, uint64_t* totals, void* workspace,
+                      void* stream);
+
+typedef struct nfec_stream_segments {  /* device arrays, as nfec_stream_frame writes them       */
+    const void* bytes;                 /* the call's byte run, any byte alignment               */
+    uint64_t stream_bytes;             /* ... and its size                                      */
+    const uint64_t* seg_start;         /* [count]                                               */
+    const uint16_t* seg_len;           /* [count]                                               */
+    const uint16_t* seg_msg_start;     /* [count]                                               */
+    uint32_t count;                    /* entries the arrays hold (upper bound)                 */
+    const uint64_t* count_dev;         /* device, may be NULL: process min(count, *count_dev)
+                                          entries (totals[0] of nfec_stream_frame)              */
+} nfec_stream_segments;
+
+/* The two copy entries.  Both are asynchronous on stream, run on the codec device that holds the
+ * batch, own no codec state, ignore batch->flags, and may run concurrently with anything
+ * (nfec_stream_pack ignores batch->num_data too: it writes num_data_out).  NFEC_EINVAL for a null pointer (except the optional arguments named below),
+ * unless 1 <= segment_size and segment_size + 8 <= vector_size, a length_stride below k when
+ * seg_length_out is given, an out_stride below k when a per-slot output is given, a mask_stride
+ * below (k + m + 31) / 32 when received is given, or stream bytes / window and batch in device
+ * memory of different devices.  A call with nothing to do (no block, or no entry and no
+ * NFEC_STREAM_END) is NFEC_OK and launches nothing.
+ *
+ * nfec_stream_pack (sender): entry i (start = seg_start[i], len = seg_len[i], ms =
+ * seg_msg_start[i]) goes to slot q = first_slot + i: block q / k of the batch, slot q % k.  The
+ * slot's bytes [0, 8) become the header {len, ms, write_offset + start}, its bytes [8, 8 + len)
+ * bytes[start, start + len) and its bytes [8 + len, vector_size) zero.  Nothing is written in
+ * [vector_size, seg_stride); the slot is never read; the stream bytes are only read, in aligned
+ * 16-byte chunks that each hold a byte of the segment.  An entry is rejected and counted, with no
+ * store, when len > segment_size, len == 0, start + len > stream_bytes or its block is >= nblocks
+ * (it keeps its slot number): a wrong table cannot make the call read outside the stream bytes or
+ * write outside the batch.  With NFEC_STREAM_END in flags the control segment of
+ * NormStreamObject::Terminate (:3904-3995) follows the last entry, at slot first_slot + (entries
+ * processed): length 0, msg_start 0, offset = write_offset + start + len of the last entry
+ * processed, or write_offset when there is none -- the stream offset behind the last emitted
+ * byte, as Terminate's Flush leaves write_offset (the caller frames its last write with FLUSH,
+ * so that nothing is carried).  seg_length_out (device [nblocks][length_stride], may be NULL):
+ * seg_length_out[b][s] = 8 + len for every slot the call fills (ReadSegment's return,
+ * :3216-3227); num_data_out (device [nblocks], may be NULL): for every block the call has a slot
+ * in, the slots of the block filled so far, counted from slot 0: min(k, first_slot + entries - b
+ * k).  These are the arrays nfec_tx_list and nfec_encode (batch.num_data) take.  stats (device
+ * [2], may be NULL; the caller zeroes it): the packed and rejected counts are added. */
+int nfec_stream_pack(const nfec_codec* codec, const nfec_stream_segments* segments, uint32_t segment_size,
+                     uint64_t first_slot, uint32_t write_offset, uint32_t flags,
+                     const nfec_block_batch* batch, uint16_t* num_data_out, uint16_t* seg_length_out,
+                     uint32_t length_stride, uint32_t* stats, void* stream);
+
+/* nfec_stream_unpack (receiver): source slot (b, s), s < k, is selected by nfec_object_write's
+ * rule (received NULL, or its bit set in received[b], or status given and status[b] > 0), within
+ * the block's nd_b = batch->num_data ? num_data[b] : k source slots: a slot at or past nd_b (a
+ * block the sender closed early, nfec_stream_pack's num_data_out) is never selected.  A slot's
+ * header is read with one aligned 8-byte load.  Length 0 is a control segment (stream end, or a
+ * slot never written: ReadPrivate :3700-3860 treats it so): counted, nothing copied.  With d =
+ * (payload_offset - base_offset) mod 2^32 the segment is invalid -- counted, nothing copied --
+ * when payload_len > segment_size (ReadPrivate's own test) or d + payload_len > window_bytes.
+ * Otherwise slot bytes [8, 8 + len) go to window[d, d + len), window (device memory, window_bytes
+ * of it) at any byte alignment.  No other byte of the window is written, or read and written
+ * back; the header is network data, and no header value makes the call write outside the window
+ * or read outside the slot's own seg_stride bytes.  Per-slot outputs, device [nblocks][out_stride],
+ * each may be NULL: offset_out the raw payload_offset, len_out payload_len (0xFFFF for a slot that
+ * was not selected; the other two are then not written), msg_start_out payload_msg_start: with
+ * them the host runs ReadPrivate's logic (contiguous prefix, message seek by msg_start - 1, stream
+ * end) on a few bytes per segment.  stats (device [4], may be NULL; the caller zeroes it):
+ * delivered, not selected, control and invalid counts are added. */
+int nfec_stream_unpack(const nfec_codec* codec, const nfec_block_batch* batch, const uint32_t* received,
+                       uint32_t mask_stride, const int32_t* status, void* window, uint64_t window_bytes,
+                       uint32_t base_offset, uint32_t segment_size, uint32_t* offset_out,
+                       uint16_t* len_out, uint16_t* msg_start_out, uint32_t out_stride, uint32_t* stats,
+                       void* stream);
 
 /* ---- host-resident batched path: same layouts, host pointers (pageable or pinned).
  * Staged through pinned buffers with H2D / compute / D2H overlapped on streams.

@@ -18,6 +18,8 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "nfec.h")
 NFEC_RS8, NFEC_RS16, NFEC_MDP = 1, 2, 3
 NFEC_OK, NFEC_EINVAL, NFEC_ENOMEM, NFEC_EDEVICE, NFEC_ERANGE, NFEC_ENOTSUP = 0, -1, -2, -3, -4, -5
 NFEC_ACCUMULATE = 1
+NFEC_STREAM_EOM, NFEC_STREAM_FLUSH = 1, 2
+NFEC_STREAM_END = 1
 NFEC_FEATURE_RS16_TOEPLITZ, NFEC_FEATURE_RS16_TOEPLITZ2 = 1, 2
 NFEC_OPT_RS16_SHARED_TABLES, NFEC_OPT_RS16_TOEPLITZ_OFF, NFEC_OPT_RS16_TOEPLITZ_ON, NFEC_OPT_HOST_ONLY = 1, 2, 4, 8
 NFEC_OPT_RS16_TOEPLITZ_ONE_LEVEL = 16
@@ -100,6 +102,30 @@ class ObjectLayout(ctypes.Structure):
         ("small_block_count", ctypes.c_uint32),
         ("final_block_id", ctypes.c_uint32),
         ("final_segment_size", ctypes.c_uint32),
+    ]
+
+
+class StreamState(ctypes.Structure):
+    """nfec_stream_state: what framing a stream's writes carries from one call to the next."""
+    _fields_ = [
+        ("write_offset", ctypes.c_uint32),
+        ("msg_start_pending", ctypes.c_uint32),
+        ("carry_bytes", ctypes.c_uint32),
+        ("carry_msg_start", ctypes.c_uint32),
+        ("next_slot", ctypes.c_uint64),
+    ]
+
+
+class StreamSegments(ctypes.Structure):
+    """nfec_stream_segments: the stream bytes and the segment table (device arrays)."""
+    _fields_ = [
+        ("bytes", ctypes.c_void_p),
+        ("stream_bytes", ctypes.c_uint64),
+        ("seg_start", ctypes.c_void_p),
+        ("seg_len", ctypes.c_void_p),
+        ("seg_msg_start", ctypes.c_void_p),
+        ("count", ctypes.c_uint32),
+        ("count_dev", ctypes.c_void_p),
     ]
 
 
@@ -211,6 +237,12 @@ _SIGS = {
                               _P]),
     "nfec_object_write": (_I, [_P, ctypes.POINTER(ObjectLayout), _P, _U64, _U32, ctypes.POINTER(BlockBatch), _P, _U32,
                                _P, _P, _P]),
+    "nfec_stream_frame_host": (_I, [_U32, _P, _P, _U32, ctypes.POINTER(StreamState), _P, _P, _P, _U32, _P]),
+    "nfec_stream_frame": (_I, [_P, _U32, _P, _P, _U32, StreamState, _P, _P, _P, _P, _U32, _P, _P, _P]),
+    "nfec_stream_pack": (_I, [_P, ctypes.POINTER(StreamSegments), _U32, _U64, _U32, _U32, ctypes.POINTER(BlockBatch), _P,
+                              _P, _U32, _P, _P]),
+    "nfec_stream_unpack": (_I, [_P, ctypes.POINTER(BlockBatch), _P, _U32, _P, _P, _U64, _U32, _U32, _P, _P, _P, _U32, _P,
+                                _P]),
     "nfec_encode_host": (_I, [_P, ctypes.POINTER(BlockBatch)]),
     "nfec_decode_host": (_I, [_P, ctypes.POINTER(BlockBatch), _P, _U32, _P, _P]),
     "nfec_encode_host_vectors": (_I, [_P, _P, _U32, _P, _U32]),
@@ -285,6 +317,11 @@ def check(rc, what):
     if rc < 0:
         raise NfecError(rc, what)
     return rc
+
+
+def stream_frame_workspace(n, capacity):
+    """NFEC_STREAM_FRAME_WORKSPACE(n, capacity) of include/nfec.h, in bytes."""
+    return (n + 2) * 40
 
 
 def source_build_id(root=None):

@@ -415,6 +415,123 @@ class _Codec:
                                           _tensor_ptr(status, "status"), _tensor_ptr(stats, "stats"),
                                           _stream_handle(stream)), "nfec_object_write")
 
+    # -- stream objects on the device (nfec.h, "stream objects on the device") --
+    def frame_stream(self, write_len, write_flags, state, segment_size=None, capacity=None, stream=None):
+        """Frame application writes of a NORM stream into segments on the device (nfec_stream_frame:
+        NormStreamObject::Write's loop).  write_len: 32-bit CUDA tensor [n]; write_flags: uint8
+        tensor [n] of NFEC_STREAM_EOM / NFEC_STREAM_FLUSH; state: the StreamState the calls before
+        left (host values).  Returns (seg_start int64, seg_len int16, seg_msg_start int16, totals
+        int64 [4], state_out): the three tables hold `capacity` entries (it must be given unless
+        there are no writes: how many segments the writes close is not known on the host),
+        totals = (segments, bytes consumed, carry bytes, carry_msg_start) and state_out is a uint8
+        tensor that holds the advanced nfec_stream_state (StreamState.from_tensor reads it).
+        totals[:1] is pack_stream's count_dev."""
+        import torch
+
+        self._need()
+        n = write_len.numel()
+        if n and (write_len.element_size() != 4 or write_flags.element_size() != 1 or write_flags.numel() != n):
+            raise ValueError("write_len must hold 32-bit lengths and write_flags as many bytes")
+        if capacity is None:
+            if n:
+                raise ValueError("capacity must be given")
+            capacity = 0
+        S = self.vector_size - 8 if segment_size is None else segment_size
+        dev = write_len.device
+        seg_start = torch.zeros(capacity, dtype=torch.int64, device=dev)
+        seg_len = torch.zeros(capacity, dtype=torch.int16, device=dev)
+        seg_ms = torch.zeros(capacity, dtype=torch.int16, device=dev)
+        totals = torch.zeros(4, dtype=torch.int64, device=dev)
+        state_out = torch.zeros(ctypes.sizeof(N.StreamState), dtype=torch.uint8, device=dev)
+        ws = torch.empty(N.stream_frame_workspace(n, capacity) // 8, dtype=torch.int64, device=dev)
+        N.check(N.lib().nfec_stream_frame(self._h, S, _tensor_ptr(write_len, "write_len") if n else None,
+                                          _tensor_ptr(write_flags, "write_flags") if n else None, n, state,
+                                          _tensor_ptr(state_out, "state_out"), _tensor_ptr(seg_start, "seg_start"),
+                                          _tensor_ptr(seg_len, "seg_len"), _tensor_ptr(seg_ms, "seg_msg_start"), capacity,
+                                          _tensor_ptr(totals, "totals"), _tensor_ptr(ws, "workspace"),
+                                          _stream_handle(stream)), "nfec_stream_frame")
+        return seg_start, seg_len, seg_ms, totals, state_out
+
+    def pack_stream(self, data, seg_start, seg_len, seg_msg_start, blocks, first_slot=0, write_offset=0, count_dev=None,
+                    end=False, segment_size=None, num_data=None, seg_length=None, stats=None, stream=None):
+        """Put framed segments of a stream into the source slots of a device batch (nfec_stream_pack):
+        the 8-byte stream payload header, the segment's bytes of `data` (uint8 CUDA tensor: the
+        byte run the table was framed over, at any alignment), zeros up to vector_size.  Entry i
+        goes to stream slot first_slot + i: block q // k, slot q % k of `blocks`.  count_dev: a
+        one-element int64 CUDA tensor (frame_stream's totals[:1]) that bounds the entries, or None;
+        end: append Terminate's zero-length control segment.  num_data: 16-bit tensor [nblocks]
+        that receives the filled slots of every touched block; seg_length: 16-bit tensor [nblocks,
+        >= k] that receives 8 + len per filled slot; stats: int32 [2], packed and rejected counts
+        are added (zero it first)."""
+        self._need()
+        b = _batch_struct(blocks, None, False)
+        count = seg_start.numel()
+        for t, size, what in ((seg_start, 8, "seg_start"), (seg_len, 2, "seg_len"), (seg_msg_start, 2, "seg_msg_start")):
+            if t.element_size() != size or t.numel() != count or not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous CUDA (HIP) tensor of {count} elements of {size} bytes")
+        if data.element_size() != 1 or not data.is_cuda or not data.is_contiguous():
+            raise ValueError("data must be a contiguous uint8 CUDA (HIP) tensor")
+        lstride = 0
+        if seg_length is not None:
+            if seg_length.dim() != 2 or seg_length.element_size() != 2 or seg_length.shape[0] != blocks.shape[0]:
+                raise ValueError("seg_length must be a 16-bit tensor [nblocks, length_stride]")
+            lstride = seg_length.shape[1]
+        if num_data is not None and (num_data.element_size() != 2 or num_data.numel() < blocks.shape[0]):
+            raise ValueError("num_data must be a 16-bit tensor [nblocks]")
+        if stats is not None and (stats.element_size() != 4 or stats.numel() < 2):
+            raise ValueError("stats must hold two 32-bit counters")
+        if count_dev is not None and (count_dev.element_size() != 8 or count_dev.numel() < 1 or not count_dev.is_cuda):
+            raise ValueError("count_dev must be a 64-bit CUDA (HIP) tensor")
+        seg = N.StreamSegments()
+        seg.bytes = data.data_ptr() if data.numel() else None
+        seg.stream_bytes = data.numel()
+        seg.seg_start, seg.seg_len, seg.seg_msg_start = seg_start.data_ptr(), seg_len.data_ptr(), seg_msg_start.data_ptr()
+        seg.count = count
+        seg.count_dev = count_dev.data_ptr() if count_dev is not None else None
+        S = self.vector_size - 8 if segment_size is None else segment_size
+        N.check(N.lib().nfec_stream_pack(self._h, ctypes.byref(seg), S, first_slot, write_offset & 0xFFFFFFFF,
+                                         N.NFEC_STREAM_END if end else 0, ctypes.byref(b),
+                                         _tensor_ptr(num_data, "num_data"), _tensor_ptr(seg_length, "seg_length"), lstride,
+                                         _tensor_ptr(stats, "stats"), _stream_handle(stream)), "nfec_stream_pack")
+
+    def unpack_stream(self, blocks, window, base_offset=0, received=None, status=None, segment_size=None, offsets=None,
+                      lengths=None, msg_starts=None, stats=None, stream=None):
+        """Deliver the stream segments in the source slots of a device batch to their bytes of
+        `window` (uint8 CUDA tensor, any alignment; its element 0 is stream offset base_offset):
+        nfec_stream_unpack.  A slot is selected as write_object selects (received / status); its
+        header says where its bytes go.  Control segments (length 0) and segments whose header asks
+        for more than segment_size bytes or for bytes outside the window are counted, not copied.
+        offsets (32-bit), lengths and msg_starts (16-bit), each [nblocks, >= k] or None, receive
+        the header fields per slot (lengths: 0xFFFF where the slot was not selected); stats: int32
+        [4], delivered / not selected / control / invalid counts are added (zero it first)."""
+        self._need()
+        b = _batch_struct(blocks, None, False)
+        if window.element_size() != 1 or not window.is_cuda or not window.is_contiguous():
+            raise ValueError("window must be a contiguous uint8 CUDA (HIP) tensor")
+        if received is not None:
+            _mask_check(received, blocks.shape[0])
+        if status is not None and (status.element_size() != 4 or status.numel() < blocks.shape[0]):
+            raise ValueError("status must be a 32-bit tensor [nblocks]")
+        if stats is not None and (stats.element_size() != 4 or stats.numel() < 4):
+            raise ValueError("stats must hold four 32-bit counters")
+        ostride = None
+        for t, size, what in ((offsets, 4, "offsets"), (lengths, 2, "lengths"), (msg_starts, 2, "msg_starts")):
+            if t is None:
+                continue
+            if t.dim() != 2 or t.element_size() != size or t.shape[0] != blocks.shape[0] or not t.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous tensor [nblocks, out_stride] of {size}-byte elements")
+            if ostride not in (None, t.shape[1]):
+                raise ValueError("offsets, lengths and msg_starts must share one out_stride")
+            ostride = t.shape[1]
+        S = self.vector_size - 8 if segment_size is None else segment_size
+        N.check(N.lib().nfec_stream_unpack(self._h, ctypes.byref(b), _tensor_ptr(received, "received"),
+                                           received.shape[1] if received is not None else 0,
+                                           _tensor_ptr(status, "status"), _tensor_ptr(window, "window"), window.numel(),
+                                           base_offset & 0xFFFFFFFF, S, _tensor_ptr(offsets, "offsets"),
+                                           _tensor_ptr(lengths, "lengths"), _tensor_ptr(msg_starts, "msg_starts"),
+                                           ostride or 0, _tensor_ptr(stats, "stats"), _stream_handle(stream)),
+                "nfec_stream_unpack")
+
     def _need(self):
         if not self._h:
             raise RuntimeError("codec not initialised (call Init)")
@@ -766,6 +883,54 @@ def object_block_sizes(layout, first_block, nblocks):
     N.check(N.lib().nfec_object_block_sizes(ctypes.byref(layout), first_block, nblocks, out.ctypes.data),
             "nfec_object_block_sizes")
     return out
+
+
+# -- stream framing (host rule, no GPU) --
+class StreamState(N.StreamState):
+    """nfec_stream_state.  StreamState() is a fresh stream: offset 0, the first write starts a message."""
+
+    def __init__(self, write_offset=0, msg_start_pending=1, carry_bytes=0, carry_msg_start=0, next_slot=0):
+        super().__init__(write_offset & 0xFFFFFFFF, msg_start_pending, carry_bytes, carry_msg_start, next_slot)
+
+    def as_tuple(self):
+        return (self.write_offset, self.msg_start_pending, self.carry_bytes, self.carry_msg_start, self.next_slot)
+
+    def copy(self):
+        return StreamState(*self.as_tuple())
+
+    @classmethod
+    def from_tensor(cls, t):
+        """The state frame_stream left in its state_out tensor (synchronizes)."""
+        s = N.StreamState.from_buffer_copy(t.cpu().numpy().tobytes())
+        return cls(s.write_offset, s.msg_start_pending, s.carry_bytes, s.carry_msg_start, s.next_slot)
+
+
+def stream_frame_host(segment_size, write_len, write_flags, state, capacity=None):
+    """nfec_stream_frame_host: frame writes of a NORM stream into segments on host arrays (no GPU).
+    write_len: 32-bit array [n]; write_flags: uint8 array [n] of NFEC_STREAM_EOM / NFEC_STREAM_FLUSH;
+    state: a StreamState, advanced in place.  Returns (seg_start uint64, seg_len uint16,
+    seg_msg_start uint16, totals uint64 [4]); the tables hold `capacity` entries (default: as many
+    as the writes close) and stay zero past the list's end; totals = (segments, bytes consumed,
+    carry bytes, carry_msg_start), the full numbers even past capacity."""
+    import numpy as np
+
+    wl = np.ascontiguousarray(write_len, dtype=np.uint32)
+    wf = np.ascontiguousarray(write_flags, dtype=np.uint8)
+    if wl.ndim != 1 or wf.shape != wl.shape:
+        raise ValueError("write_len and write_flags must be one-dimensional and of one length")
+    totals = np.zeros(4, np.uint64)
+    if capacity is None:  # a counting call on a copy of the state
+        probe = N.StreamState.from_buffer_copy(bytes(state))
+        N.check(N.lib().nfec_stream_frame_host(segment_size, wl.ctypes.data, wf.ctypes.data, wl.size, ctypes.byref(probe),
+                                               None, None, None, 0, totals.ctypes.data), "nfec_stream_frame_host")
+        capacity = int(totals[0])
+    seg_start = np.zeros(capacity, np.uint64)
+    seg_len = np.zeros(capacity, np.uint16)
+    seg_ms = np.zeros(capacity, np.uint16)
+    N.check(N.lib().nfec_stream_frame_host(segment_size, wl.ctypes.data, wf.ctypes.data, wl.size, ctypes.byref(state),
+                                           seg_start.ctypes.data, seg_len.ctypes.data, seg_ms.ctypes.data, capacity,
+                                           totals.ctypes.data), "nfec_stream_frame_host")
+    return seg_start, seg_len, seg_ms, totals
 
 
 # -- synthetic workload helpers (device kernels) --

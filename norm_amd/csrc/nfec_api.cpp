@@ -999,6 +999,118 @@ int nfec_object_write(const nfec_codec* codec, const nfec_object_layout* layout,
     return launch_obj_write(a, static_cast<hipStream_t>(stream));
 }
 
+// ---- stream objects on the device (kernels_stream.hip) ----
+// Arguments first, then the codec's device, as above.
+int nfec_stream_frame(const nfec_codec* codec, uint32_t segment_size, const uint32_t* write_len, const uint8_t* write_flags,
+                      uint32_t n, nfec_stream_state state, nfec_stream_state* state_out, uint64_t* seg_start,
+                      uint16_t* seg_len, uint16_t* seg_msg_start, uint32_t capacity, uint64_t* totals, void* workspace,
+                      void* stream)
+{
+    if (!codec) return fail(NFEC_EINVAL, "null codec");
+    if (!state_out || !totals || !workspace) return fail(NFEC_EINVAL, "stream_frame: null state_out, totals or workspace");
+    if (n && (!write_len || !write_flags)) return fail(NFEC_EINVAL, "stream_frame: null write arrays");
+    if (n == 0xffffffffu) return fail(NFEC_EINVAL, "stream_frame: more than 2^32 - 2 writes");
+    if (capacity && (!seg_start || !seg_len || !seg_msg_start)) return fail(NFEC_EINVAL, "stream_frame: null output array");
+    int rc = check_stream_frame(segment_size, &state);
+    if (rc) return rc;
+    if (primary(codec)->host_only) return host_only_fail();
+    const nfec_codec* c = stripe_for(const_cast<nfec_codec*>(codec), totals);
+    if (!c) return fail(NFEC_EINVAL, "totals is not on a device of the codec");
+    DeviceGuard g(c->device);
+    StreamFrameArgs a;
+    a.S = segment_size;
+    a.write_len = write_len;
+    a.write_flags = write_flags;
+    a.n = n;
+    a.state = state;
+    a.state_out = state_out;
+    a.seg_start = seg_start;
+    a.seg_len = seg_len;
+    a.seg_msg_start = seg_msg_start;
+    a.capacity = capacity;
+    a.totals = totals;
+    a.ws = static_cast<uint64_t*>(workspace);
+    return launch_stream_frame(a, static_cast<hipStream_t>(stream));
+}
+
+static int check_stream_copy(const nfec_codec* codec, const nfec_block_batch* batch, uint32_t segment_size)
+{
+    if (!codec || !batch) return fail(NFEC_EINVAL, "null codec or batch");
+    if (segment_size < 1 || (uint64_t)segment_size + 8u > codec->vec)
+        return fail(NFEC_EINVAL, "segment_size outside [1, vector_size - 8]");
+    return NFEC_OK;
+}
+
+int nfec_stream_pack(const nfec_codec* codec, const nfec_stream_segments* seg, uint32_t segment_size, uint64_t first_slot,
+                     uint32_t write_offset, uint32_t flags, const nfec_block_batch* batch, uint16_t* num_data_out,
+                     uint16_t* seg_length_out, uint32_t length_stride, uint32_t* stats, void* stream)
+{
+    if (!seg) return fail(NFEC_EINVAL, "null segments");
+    int rc = check_stream_copy(codec, batch, segment_size);
+    if (rc) return rc;
+    if (flags & ~NFEC_STREAM_END) return fail(NFEC_EINVAL, "stream_pack: unknown flags");
+    if (seg->count && (!seg->seg_start || !seg->seg_len || !seg->seg_msg_start))
+        return fail(NFEC_EINVAL, "null segments->seg_start, seg_len or seg_msg_start");
+    if (seg->count && !seg->bytes) return fail(NFEC_EINVAL, "null segments->bytes");
+    if (seg_length_out && length_stride < codec->k) return fail(NFEC_EINVAL, "length_stride < k");
+    if (first_slot > (1ull << 63)) return fail(NFEC_EINVAL, "first_slot above 2^63");
+    const uint32_t end = flags & NFEC_STREAM_END ? 1u : 0u;
+    if ((rc = check_batch(codec, batch)) || batch->nblocks == 0 || (seg->count == 0 && !end)) return rc;
+    const nfec_codec* c = seg->bytes ? object_stripe(codec, seg->bytes, batch)
+                                     : stripe_for(const_cast<nfec_codec*>(codec), batch->blocks);
+    if (!c) return seg->bytes ? NFEC_EINVAL : fail(NFEC_EINVAL, "batch is not on a device of the codec");
+    DeviceGuard g(c->device);
+    StreamPackArgs a;
+    a.batch = batch_view(c, batch);
+    a.bytes = static_cast<const uint8_t*>(seg->bytes);
+    a.stream_bytes = seg->stream_bytes;
+    a.seg_start = seg->seg_start;
+    a.seg_len = seg->seg_len;
+    a.seg_msg_start = seg->seg_msg_start;
+    a.count = seg->count;
+    a.count_dev = seg->count ? seg->count_dev : nullptr;
+    a.S = segment_size;
+    a.first_slot = first_slot;
+    a.write_offset = write_offset;
+    a.end = end;
+    a.num_data_out = num_data_out;
+    a.seg_length_out = seg_length_out;
+    a.length_stride = length_stride;
+    a.stats = stats;
+    return launch_stream_pack(a, static_cast<hipStream_t>(stream));
+}
+
+int nfec_stream_unpack(const nfec_codec* codec, const nfec_block_batch* batch, const uint32_t* received,
+                       uint32_t mask_stride, const int32_t* status, void* window, uint64_t window_bytes,
+                       uint32_t base_offset, uint32_t segment_size, uint32_t* offset_out, uint16_t* len_out,
+                       uint16_t* msg_start_out, uint32_t out_stride, uint32_t* stats, void* stream)
+{
+    int rc = check_stream_copy(codec, batch, segment_size);
+    if (rc) return rc;
+    if (!window) return fail(NFEC_EINVAL, "null window");
+    if (received && (rc = check_mask(codec, received, mask_stride))) return rc;
+    if ((offset_out || len_out || msg_start_out) && out_stride < codec->k) return fail(NFEC_EINVAL, "out_stride < k");
+    if ((rc = check_batch(codec, batch)) || batch->nblocks == 0) return rc;
+    const nfec_codec* c = object_stripe(codec, window, batch);
+    if (!c) return NFEC_EINVAL;
+    DeviceGuard g(c->device);
+    StreamUnpackArgs a;
+    a.batch = batch_view(c, batch);
+    a.received = received;
+    a.mask_stride = mask_stride;
+    a.status = status;
+    a.window = static_cast<uint8_t*>(window);
+    a.window_bytes = window_bytes;
+    a.base_offset = base_offset;
+    a.S = segment_size;
+    a.offset_out = offset_out;
+    a.len_out = len_out;
+    a.msg_start_out = msg_start_out;
+    a.out_stride = out_stride;
+    a.stats = stats;
+    return launch_stream_unpack(a, static_cast<hipStream_t>(stream));
+}
+
 // ---- per-call NORM semantics (synchronous, host vectors) ----
 // One call = gather the caller's vectors into the codec's pinned staging (host memcpy), one
 // H2D copy, the kernels, one D2H copy of what the call writes, one synchronize, scatter.  The

@@ -866,4 +866,60 @@ struct ObjArgs {
 int launch_obj_read(const ObjArgs& a, hipStream_t s);
 int launch_obj_write(const ObjArgs& a, hipStream_t s);
 
+// Stream objects on the device (kernels_stream.hip; nfec.h "stream objects on the device").
+// Frame: the writes' scans by one workgroup (tiles with a running carry, as tx_list's scan), then
+// one lane per segment.  Pack / unpack: the object kernels' walk with a table-driven / header-
+// driven source and length per segment.
+int check_stream_frame(uint32_t segment_size, const nfec_stream_state* state);  // (stream.cpp)
+struct StreamFrameArgs {
+    uint32_t S = 0;
+    const uint32_t* write_len = nullptr;   // [n]
+    const uint8_t* write_flags = nullptr;  // [n]
+    uint32_t n = 0;
+    nfec_stream_state state{};
+    nfec_stream_state* state_out = nullptr;
+    uint64_t* seg_start = nullptr;
+    uint16_t* seg_len = nullptr;
+    uint16_t* seg_msg_start = nullptr;
+    uint32_t capacity = 0;
+    uint64_t* totals = nullptr;            // [4]
+    uint64_t* ws = nullptr;                // [5][n + 2]
+};
+int launch_stream_frame(const StreamFrameArgs& a, hipStream_t s);
+struct StreamPackArgs {
+    BatchView batch;
+    const uint8_t* bytes = nullptr;
+    uint64_t stream_bytes = 0;
+    const uint64_t* seg_start = nullptr;
+    const uint16_t* seg_len = nullptr;
+    const uint16_t* seg_msg_start = nullptr;
+    uint32_t count = 0;
+    const uint64_t* count_dev = nullptr;   // device, or null: min(count, *count_dev) entries
+    uint32_t S = 0;
+    uint64_t first_slot = 0;
+    uint32_t write_offset = 0;
+    uint32_t end = 0;                      // 1: the control segment follows the last entry
+    uint16_t* num_data_out = nullptr;      // [nblocks], or null
+    uint16_t* seg_length_out = nullptr;    // [nblocks][length_stride], or null
+    uint32_t length_stride = 0;
+    uint32_t* stats = nullptr;             // [2] packed, rejected (or null)
+};
+int launch_stream_pack(const StreamPackArgs& a, hipStream_t s);
+struct StreamUnpackArgs {
+    BatchView batch;                       // (only read)
+    const uint32_t* received = nullptr;    // [nblocks][mask_stride], or null = every segment
+    uint32_t mask_stride = 0;
+    const int32_t* status = nullptr;       // [nblocks], or null
+    uint8_t* window = nullptr;
+    uint64_t window_bytes = 0;
+    uint32_t base_offset = 0;
+    uint32_t S = 0;
+    uint32_t* offset_out = nullptr;        // [nblocks][out_stride], or null
+    uint16_t* len_out = nullptr;
+    uint16_t* msg_start_out = nullptr;
+    uint32_t out_stride = 0;
+    uint32_t* stats = nullptr;             // [4] delivered, not selected, control, invalid (or null)
+};
+int launch_stream_unpack(const StreamUnpackArgs& a, hipStream_t s);
+
 }  // namespace nfec

@@ -342,6 +342,86 @@ int nfec_rx_erasures_host(uint32_t k, uint32_t m, const uint32_t* received, uint
                           const uint16_t* num_data, uint32_t nblocks, uint16_t* erasure_locs,
                           uint32_t erasure_stride, uint16_t* erasure_counts);
 
+/* ---- repair requests on the device ----
+ * The step of the receiver's cycle that leads back to the sender's pending masks: the repair-request
+ * content of a NORM_NACK from the reception masks in HBM, as NormObject::AppendRepairRequest builds it
+ * with flush set and nacking_mode NACK_NORMAL (normObject.cpp:1179-1381) and, per block,
+ * NormBlock::AppendRepairRequest (normSegment.cpp:524-630).  The caller bounds the call at the last
+ * block the sender has finished; the max_pending_block / max_pending_segment form, the NACK's message
+ * header, its timers, back-off and suppression stay the caller's, as does what the sender does with
+ * a NACK beyond parsing it (hold-off, transmit index, order across receivers).
+ *
+ * Per block, with nd_b = num_data ? num_data[b] : k and "pending" a clear bit of the reception mask
+ * in [0, nd_b + m): e = pending source slots, p = received parity slots.  A block is
+ *   absent  (class 2) when no bit of [0, nd_b + m) is set (the reference holds no NormBlock for it),
+ *   needing (class 1) when it is not absent and e > p,
+ *   silent  (class 0) otherwise: complete, decodable (0 < e <= p: what nfec_decode_received
+ *           repairs), or nd_b outside [1, k].
+ * A needing block asks for (normSegment.cpp:536-554): with e > m every pending slot of [0, nd_b + m)
+ * except the first m pending ones, otherwise the pending slots of [nd_b, nd_b + e).  A maximal run
+ * of consecutive requested slots is one unit (:562-621): a run of 1 or 2 is an ITEMS unit of one or
+ * two items, a run of 3 or more a RANGES unit of two items, its first and last slot.  The units of a
+ * needing block form one chain; its requests carry flag SEGMENT (0x01).
+ * Across blocks (normObject.cpp:1207-1278) a maximal run of consecutive absent blocks is a unit of
+ * the same three kinds, every item with symbol 0 and its own block's nd (a range: the first and the
+ * last block's), flag BLOCK (0x02).  A chain of block-level units runs from one needing block (or
+ * the start) to the next (or the end); silent blocks separate its units but do not end it.  Output
+ * is in block order: a run's unit is emitted at the position of the run's last block, and a chain's
+ * units stand before the needing block that ends it.
+ * Walking a chain, a unit opens a new request when it is the chain's first, when its form differs
+ * from the previous unit's, or when the open request holds max_units units already.  The last is a
+ * bound the caller controls where the reference stops at a full NACK: with max_units at least the
+ * longest same-form stretch the bytes are what the reference's calls append to an unbounded NACK.
+ * A request is form (u8: ITEMS 1, RANGES 2), flags (u8), length of its items in bytes (u16,
+ * big-endian), then the items (NormRepairRequest::Pack, normMessage.cpp:263-276); an item is fec_id
+ * (u8), 0 (u8), object id (u16, big-endian), then the bytes nfec_payload_id_write writes for
+ * (first_block_id + b, symbol, nd_b) (AppendRepairItem / AppendRepairRange, :163-235).  Everything
+ * is a multiple of 4 bytes.  With NFEC_NACK_INFO every request also carries INFO (0x04), and when
+ * nothing else was produced the content is the INFO-only request (normObject.cpp:1365-1372): ITEMS,
+ * flags INFO, one item with block 0, block length 0, symbol 0. */
+#define NFEC_NACK_INFO 1u   /* flags: the object's NORM_INFO is pending too */
+
+/* content: device, 4-byte aligned, `capacity` bytes; bytes at or past capacity and bytes at or past
+ * the total are not written.  block_start: device uint64 [nblocks + 1][2], the call's workspace and
+ * an output: row b = {bytes emitted at positions before b, that is the offset of the first request
+ * byte emitted at block b's position; block b's class 0 / 1 / 2}, row nblocks = {bytes, requests}.
+ * totals: device uint64 [4] = {bytes, requests, needing blocks, absent blocks}, the full numbers even
+ * past capacity (nfec_tx_list's rule).  Asynchronous on stream, on the codec device that holds the
+ * mask; owns no codec state; the mask is only read.  NFEC_EINVAL for a fec_id / fec_m pair
+ * nfec_payload_id_write refuses and for fec_id 0, for flags other than NFEC_NACK_INFO, for max_units
+ * of 0 or above 65535 / (2 * item length) (item length = 4 + nfec_payload_id_length(fec_id)), for
+ * null arrays, a content that is not 4-byte aligned and a mask_stride below (k + m + 31) / 32.
+ * nblocks == 0 is NFEC_OK and writes zero totals. */
+int nfec_rx_repair_requests(const nfec_codec* codec, const uint32_t* received, uint32_t mask_stride,
+                            const uint16_t* num_data, uint32_t nblocks, uint8_t fec_id, uint8_t fec_m,
+                            uint16_t object_id, uint32_t first_block_id, uint32_t flags, uint32_t max_units,
+                            void* content, uint64_t capacity, uint64_t* block_start, uint64_t* totals,
+                            void* stream);
+/* nfec_rx_repair_requests' rule on host arrays: no codec, no GPU (content at any alignment).  Also
+ * NFEC_EINVAL for k or m of 0 and k + m > 65536. */
+int nfec_rx_repair_requests_host(uint32_t k, uint32_t m, const uint32_t* received, uint32_t mask_stride,
+                                 const uint16_t* num_data, uint32_t nblocks, uint8_t fec_id, uint8_t fec_m,
+                                 uint16_t object_id, uint32_t first_block_id, uint32_t flags,
+                                 uint32_t max_units, void* content, uint64_t capacity, uint64_t* block_start,
+                                 uint64_t* totals);
+/* The parser of repair-request content, for the sender's side and for tests: NormRepairRequest::
+ * Unpack (normMessage.cpp:279-305) and ::Iterator (:335-358) over content[0, bytes) in host memory.
+ * Unit u < capacity gets unit_flags[u], unit_form[u] and first[u] / last[u] = {object id, block id
+ * as on the wire, block length (fec_id 129; else 0), symbol}; every item of a request that is not
+ * RANGES is a unit with first = last.  The arrays are [capacity] / [capacity][4] and may be NULL.
+ * It stops at a header that does not fit or whose length exceeds what is left, at a RANGES request
+ * with an odd item count, and at an item with a foreign fec_id (a range: either of its items); a
+ * request's bytes behind its last whole item are skipped.  Returns the number of units read before
+ * the stop, even past capacity; *consumed (may be NULL) = the offset of the header or item it
+ * stopped at, or bytes.  NFEC_EINVAL for a refused fec_id / fec_m pair or a null content with bytes
+ * > 0, NFEC_ERANGE for more than 2^31 - 1 units. */
+int nfec_repair_parse_host(uint8_t fec_id, uint8_t fec_m, const void* content, uint64_t bytes,
+                           uint8_t* unit_flags, uint8_t* unit_form, uint32_t* first, uint32_t* last,
+                           uint32_t capacity, uint64_t* consumed);
+/* The operator of the kernels' segmented scans on {value, flag} pairs, out = a then b (for the host
+ * test of its associativity). */
+void nfec_nack_scan_combine_host(const uint64_t a[2], const uint64_t b[2], uint64_t out[2]);
+
 /* ---- sender assembly on the device ----
  * What NormObject::NextSenderMsg does once a block's parity exists (normObject.cpp:1877-2078) for
  * a sender whose blocks are in HBM: walk the blocks and their pending masks in order, pick each
@@ -354,7 +434,8 @@ int nfec_rx_erasures_host(uint32_t k, uint32_t m, const uint32_t* received, uint
  * A pending mask has the reception mask's layout: uint32_t pending[nblocks][mask_stride],
  * mask_stride >= (k + m + 31) / 32, bit s % 32 of word s / 32 is slot s.  The caller sets it as
  * NormBlock::TxInit does (normSegment.h:106-118: bits [0, numData + autoParity)) and as TxUpdate /
- * ActivateRepairs do (normSegment.cpp:261-339).  Bits at or past numData_b + m are ignored.
+ * ActivateRepairs do (normSegment.cpp:261-339) from what nfec_repair_parse_host reads out of a
+ * NACK.  Bits at or past numData_b + m are ignored.
  *
  * The transmission list.  With nd_b = num_data ? num_data[b] : k (device [nblocks] or NULL), the
  * entries are: blocks ascending, within a block the pending slots of [0, nd_b + m) ascending

@@ -20,6 +20,11 @@ NFEC_OK, NFEC_EINVAL, NFEC_ENOMEM, NFEC_EDEVICE, NFEC_ERANGE, NFEC_ENOTSUP = 0, 
 NFEC_ACCUMULATE = 1
 NFEC_STREAM_EOM, NFEC_STREAM_FLUSH = 1, 2
 NFEC_STREAM_END = 1
+NFEC_NACK_INFO = 1
+# nfec_rx_repair_requests: a block's class, a request's form and flags
+NACK_SILENT, NACK_NEEDING, NACK_ABSENT = 0, 1, 2
+REPAIR_ITEMS, REPAIR_RANGES = 1, 2
+REPAIR_SEGMENT, REPAIR_BLOCK, REPAIR_INFO = 1, 2, 4
 NFEC_FEATURE_RS16_TOEPLITZ, NFEC_FEATURE_RS16_TOEPLITZ2 = 1, 2
 NFEC_OPT_RS16_SHARED_TABLES, NFEC_OPT_RS16_TOEPLITZ_OFF, NFEC_OPT_RS16_TOEPLITZ_ON, NFEC_OPT_HOST_ONLY = 1, 2, 4, 8
 NFEC_OPT_RS16_TOEPLITZ_ONE_LEVEL = 16
@@ -226,6 +231,11 @@ _SIGS = {
     "nfec_rx_erasures": (_I, [_P, _P, _U32, _P, _U32, _P, _U32, _P, _P]),
     "nfec_decode_received": (_I, [_P, ctypes.POINTER(BlockBatch), _P, _U32, _P, _P]),
     "nfec_rx_erasures_host": (_I, [_U32, _U32, _P, _U32, _P, _U32, _P, _U32, _P]),
+    "nfec_rx_repair_requests": (_I, [_P, _P, _U32, _P, _U32, _U8, _U8, _U16, _U32, _U32, _U32, _P, _U64, _P, _P, _P]),
+    "nfec_rx_repair_requests_host": (_I, [_U32, _U32, _P, _U32, _P, _U32, _U8, _U8, _U16, _U32, _U32, _U32, _P, _U64, _P,
+                                          _P]),
+    "nfec_repair_parse_host": (_I, [_U8, _U8, _P, _U64, _P, _P, _P, _P, _U32, ctypes.POINTER(_U64)]),
+    "nfec_nack_scan_combine_host": (None, [_P, _P, _P]),
     "nfec_tx_list": (_I, [_P, _P, _U32, _P, _U32, _P, _U32, _U32, _P, _P, _P, _P, _U32, _P, _P]),
     "nfec_tx_list_host": (_I, [_U32, _U32, _U32, _P, _U32, _P, _U32, _P, _U32, _U32, _P, _P, _P, _P, _U32, _P]),
     "nfec_tx_emit": (_I, [_P, ctypes.POINTER(BlockBatch), ctypes.POINTER(TxSegments), _U8, _U8, _U32, _P, _U32, _P,

@@ -294,6 +294,35 @@ class _Codec:
                                          _tensor_ptr(counts, "counts"), _stream_handle(stream)), "nfec_rx_erasures")
         return locs, counts
 
+    def repair_requests(self, received, num_data=None, fec_id=5, fec_m=8, object_id=0, first_block_id=0, flags=0,
+                        max_units=None, capacity=None, content=None, stream=None):
+        """The repair-request content of a NORM_NACK from a reception mask (nfec_rx_repair_requests):
+        (content uint8 [capacity], block_start int64 [nblocks + 1, 2], totals int64 [4]).  totals =
+        (bytes, requests, needing blocks, absent blocks), the full numbers even past capacity;
+        block_start[b] = (offset of what is emitted at block b's position, the block's class 0 / 1 / 2
+        for silent / needing / absent).  max_units defaults to the most a request may hold;
+        capacity to what every block's longest content needs (`content`: a uint8 tensor to write
+        into instead, 4-byte aligned).  The mask is only read."""
+        import torch
+
+        self._need()
+        _mask_check(received, received.shape[0])
+        nb = received.shape[0]
+        max_units = repair_max_units(fec_id) if max_units is None else max_units
+        if content is None:
+            capacity = repair_content_bound(self.ndata, self.npar, nb, fec_id) if capacity is None else capacity
+            content = torch.zeros(capacity, dtype=torch.uint8, device=received.device)
+        capacity = content.numel() if capacity is None else capacity
+        block_start = torch.zeros((nb + 1, 2), dtype=torch.int64, device=received.device)
+        totals = torch.zeros(4, dtype=torch.int64, device=received.device)
+        N.check(N.lib().nfec_rx_repair_requests(self._h, _tensor_ptr(received, "received"), received.shape[1],
+                                                _tensor_ptr(num_data, "num_data"), nb, fec_id, fec_m, object_id & 0xFFFF,
+                                                first_block_id & 0xFFFFFFFF, flags, max_units,
+                                                _tensor_ptr(content, "content"), capacity,
+                                                _tensor_ptr(block_start, "block_start"), _tensor_ptr(totals, "totals"),
+                                                _stream_handle(stream)), "nfec_rx_repair_requests")
+        return content, block_start, totals
+
     # -- sender assembly on the device (nfec.h, "sender assembly on the device") --
     def list_pending(self, pending, num_data=None, seg_length=None, gap=0, capacity=None, stream=None):
         """The transmission list of a pending mask (nfec_tx_list), in NextSenderMsg's order:
@@ -822,6 +851,64 @@ def rx_parse_host(fec_id, fec_m, first_block_id, wire, offsets, length):
                                        off.ctypes.data, ln.ctypes.data, off.size, block_index.ctypes.data,
                                        symbol_id.ctypes.data, block_len.ctypes.data), "nfec_rx_parse_host")
     return block_index, symbol_id, block_len
+
+
+def repair_max_units(fec_id):
+    """The largest max_units nfec_rx_repair_requests takes: 65535 / (2 * item length)."""
+    return 65535 // (2 * (4 + N.lib().nfec_payload_id_length(fec_id)))
+
+
+def repair_content_bound(k, m, nblocks, fec_id):
+    """Bytes that hold the repair-request content of any nblocks masks: at most every other slot of
+    a block (or every other block) starts a unit of two items with a header of its own."""
+    item = 4 + N.lib().nfec_payload_id_length(fec_id)
+    return nblocks * ((k + m + 1) // 2) * (4 + 2 * item) + 4 + 2 * item
+
+
+def rx_repair_requests_host(k, m, received, num_data=None, fec_id=5, fec_m=8, object_id=0, first_block_id=0, flags=0,
+                            max_units=None, capacity=None):
+    """nfec_rx_repair_requests_host: the repair-request content of reception masks in host memory
+    (no GPU).  received: NumPy 32-bit array [nblocks, mask_stride].  Returns (content uint8
+    [capacity], block_start uint64 [nblocks + 1, 2], totals uint64 [4]) as Codec.repair_requests."""
+    import numpy as np
+
+    mask = np.ascontiguousarray(received).view(np.uint32)
+    if mask.ndim != 2:
+        raise ValueError("received must be a 32-bit array [nblocks, mask_stride]")
+    nb = mask.shape[0]
+    max_units = repair_max_units(fec_id) if max_units is None else max_units
+    capacity = repair_content_bound(k, m, nb, fec_id) if capacity is None else capacity
+    nd = None if num_data is None else np.ascontiguousarray(num_data, dtype=np.uint16)
+    content = np.zeros(capacity, np.uint8)
+    block_start = np.zeros((nb + 1, 2), np.uint64)
+    totals = np.zeros(4, np.uint64)
+    N.check(N.lib().nfec_rx_repair_requests_host(k, m, mask.ctypes.data, mask.shape[1],
+                                                 None if nd is None else nd.ctypes.data, nb, fec_id, fec_m,
+                                                 object_id & 0xFFFF, first_block_id & 0xFFFFFFFF, flags, max_units,
+                                                 content.ctypes.data, capacity, block_start.ctypes.data,
+                                                 totals.ctypes.data), "nfec_rx_repair_requests_host")
+    return content, block_start, totals
+
+
+def repair_parse_host(fec_id, fec_m, content, capacity=None):
+    """nfec_repair_parse_host: the units of repair-request content (NumPy uint8 array), as the sender
+    reads a NACK.  Returns (flags uint8 [n], form uint8 [n], first uint32 [n, 4], last uint32 [n, 4],
+    consumed): first / last = (object id, block id as on the wire, block length, symbol), n the units
+    read before the parser stopped, consumed the offset it stopped at."""
+    import numpy as np
+
+    buf = np.ascontiguousarray(content).view(np.uint8).reshape(-1)
+    capacity = buf.size // 8 + 1 if capacity is None else capacity
+    flags = np.zeros(capacity, np.uint8)
+    form = np.zeros(capacity, np.uint8)
+    first = np.zeros((capacity, 4), np.uint32)
+    last = np.zeros((capacity, 4), np.uint32)
+    consumed = ctypes.c_uint64(0)
+    n = N.check(N.lib().nfec_repair_parse_host(fec_id, fec_m, buf.ctypes.data, buf.size, flags.ctypes.data,
+                                               form.ctypes.data, first.ctypes.data, last.ctypes.data, capacity,
+                                               ctypes.byref(consumed)), "nfec_repair_parse_host")
+    n = min(n, capacity)
+    return flags[:n], form[:n], first[:n], last[:n], consumed.value
 
 
 def tx_list_host(k, m, vector_size, pending, num_data=None, seg_length=None, gap=0, capacity=None):

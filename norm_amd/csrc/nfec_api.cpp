@@ -22,6 +22,7 @@
 
 #include "bitslice.hpp"
 #include "codec_state.hpp"
+#include "nack_layout.hpp"
 #include "rx_parse.hpp"
 
 using namespace nfec;
@@ -824,6 +825,45 @@ int nfec_decode_received(nfec_codec* codec, const nfec_block_batch* batch, const
     a.counts = codec->ws.rxcounts.p;
     if ((rc = launch_rx_erasures(a, s))) return rc;
     return decode_device(codec, batch, codec->ws.rxlocs.p, lstride, codec->ws.rxcounts.p, status, s, true);
+}
+
+// ---- repair requests on the device (kernels_nack.hip) ----
+int nfec_rx_repair_requests(const nfec_codec* codec, const uint32_t* received, uint32_t mask_stride,
+                            const uint16_t* num_data, uint32_t nblocks, uint8_t fec_id, uint8_t fec_m, uint16_t object_id,
+                            uint32_t first_block_id, uint32_t flags, uint32_t max_units, void* content, uint64_t capacity,
+                            uint64_t* block_start, uint64_t* totals, void* stream)
+{
+    if (!codec) return fail(NFEC_EINVAL, "null codec");
+    NackFormat f;
+    int rc = nack_format(fec_id, fec_m, object_id, first_block_id, flags, max_units, &f);
+    if (rc) return rc;
+    if (nblocks && (rc = check_mask(codec, received, mask_stride))) return rc;
+    if (!block_start || !totals) return fail(NFEC_EINVAL, "null block_start or totals");
+    if (capacity && !content) return fail(NFEC_EINVAL, "null content");
+    if (reinterpret_cast<uintptr_t>(content) & 3u) return fail(NFEC_EINVAL, "content is not 4-byte aligned");
+    if (primary(codec)->host_only) return host_only_fail();
+    const nfec_codec* c = stripe_for(const_cast<nfec_codec*>(codec), nblocks ? (const void*)received : block_start);
+    if (!c) return fail(NFEC_EINVAL, "received mask is not on a device of the codec");
+    DeviceGuard g(c->device);
+    NackArgs a;
+    a.received = received;
+    a.mask_stride = mask_stride;
+    a.num_data = num_data;
+    a.k = c->k;
+    a.m = c->m;
+    a.nblocks = nblocks;
+    a.id_kind = f.id_kind;
+    a.item_len = f.item_len;
+    a.fec_id = f.fec_id;
+    a.object_id = f.object_id;
+    a.first_block_id = f.first_block_id;
+    a.info = f.info;
+    a.max_units = f.max_units;
+    a.content = static_cast<uint8_t*>(content);
+    a.capacity = capacity;
+    a.rows = block_start;
+    a.totals = totals;
+    return launch_nack(a, static_cast<hipStream_t>(stream));
 }
 
 // ---- sender assembly on the device (kernels_tx.hip) ----

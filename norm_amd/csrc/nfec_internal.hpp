@@ -844,6 +844,32 @@ struct TxEmitArgs {
 };
 int launch_tx_emit(const TxEmitArgs& a, hipStream_t s);
 
+// Repair requests on the device (kernels_nack.hip; nfec.h "repair requests on the device").  The
+// shape of the transmission list: per-block classes, bytes and requests (one wave per block) into
+// block_start, one workgroup's scans over the blocks (byte offsets and the chains of block-level
+// units), and the per-block expansion into the content.
+struct NackArgs {
+    const uint32_t* received = nullptr;    // [nblocks][mask_stride], only read
+    uint32_t mask_stride = 0;
+    const uint16_t* num_data = nullptr;    // per block, or null = k
+    uint32_t k = 0, m = 0;
+    uint32_t nblocks = 0;
+    uint32_t id_kind = 0;                  // the payload ID's layout (PAYLOAD_ID_*, rx_parse.hpp)
+    uint32_t item_len = 0;                 // 4 + the payload ID's length
+    uint32_t fec_id = 0, object_id = 0, first_block_id = 0;
+    uint32_t info = 0;                     // REPAIR_INFO or 0
+    uint32_t max_units = 0;
+    uint8_t* content = nullptr;            // [capacity], 4-byte aligned
+    uint64_t capacity = 0;
+    uint64_t* rows = nullptr;              // block_start [nblocks + 1][2]
+    uint64_t* totals = nullptr;            // [4]
+};
+int launch_nack(const NackArgs& a, hipStream_t s);
+struct NackFormat;
+// the argument checks the device and the host entry share (nack_host.cpp)
+int nack_format(uint8_t fec_id, uint8_t fec_m, uint16_t object_id, uint32_t first_block_id, uint32_t flags,
+                uint32_t max_units, NackFormat* f);
+
 // Object segmentation on the device (kernels_obj.hip; nfec.h "object segmentation on the device").
 // One workgroup per run of up to 64 consecutive segments of a block; its lanes stride over the
 // run's (segment, 16-byte piece) pairs as one flat index.  Read: the object's bytes, at any

@@ -31,6 +31,10 @@
  *   nfec_tx_list / nfec_tx_emit
  *                         the pending walk, the payload lengths, the FEC payload ID and UnsetPending
  *                         of NormObject::NextSenderMsg  src/common/normObject.cpp:1877-2078
+ *   nfec_tx_handle_nacks / nfec_tx_activate_repairs / nfec_tx_end_blocks
+ *                         NormSession::SenderHandleNackMessage (!holdoff)  src/common/normSession.cpp:3706-4300,
+ *                         NormBlock::HandleSegmentRequest  src/common/normSegment.cpp:341-402, OnRepairTimeout
+ *                         normSession.cpp:4720-4750 and ResetParityCount  src/common/normObject.cpp:2079-2083
  *   nfec_object_layout_for / nfec_object_read / nfec_object_write
  *                         the block partition of NormObject::Open  src/common/normObject.cpp:134-137,
  *                         :203-231, NormDataObject::ReadSegment :2673-2718 and WriteSegment :2628-2670
@@ -435,7 +439,8 @@ void nfec_nack_scan_combine_host(const uint64_t a[2], const uint64_t b[2], uint6
  * mask_stride >= (k + m + 31) / 32, bit s % 32 of word s / 32 is slot s.  The caller sets it as
  * NormBlock::TxInit does (normSegment.h:106-118: bits [0, numData + autoParity)) and as TxUpdate /
  * ActivateRepairs do (normSegment.cpp:261-339) from what nfec_repair_parse_host reads out of a
- * NACK.  Bits at or past numData_b + m are ignored.
+ * NACK, or lets nfec_tx_activate_repairs set it ("sender repair state on the device").  Bits at or
+ * past numData_b + m are ignored.
  *
  * The transmission list.  With nd_b = num_data ? num_data[b] : k (device [nblocks] or NULL), the
  * entries are: blocks ascending, within a block the pending slots of [0, nd_b + m) ascending
@@ -495,6 +500,147 @@ typedef struct nfec_tx_segments {      /* device arrays, as nfec_tx_list writes 
 int nfec_tx_emit(const nfec_codec* codec, const nfec_block_batch* batch, const nfec_tx_segments* segments,
                  uint8_t fec_id, uint8_t fec_m, uint32_t first_block_id, uint32_t* pending,
                  uint32_t mask_stride, uint32_t* stats, void* stream);
+
+/* ---- sender repair state on the device ----
+ * The step that closes the cycle: from the repair-request content of the NACKs of one repair cycle
+ * (the bytes nfec_rx_repair_requests writes, behind each NORM_NACK's own header) to the pending
+ * masks nfec_tx_list reads, by NORM's repair economy: a sender that holds m parity segments answers
+ * "e segments of block b are missing" with e fresh parity segments, aggregates over the receivers
+ * of a cycle (the largest e is what gets sent) and retransmits named segments only once the parity
+ * is used up.  In the reference: NormSession::SenderHandleNackMessage, the !holdoff arm
+ * (normSession.cpp:3706-4300), NormBlock::HandleSegmentRequest (normSegment.cpp:341-402),
+ * NormObject::HandleBlockRequest (normObject.cpp:352-385), NormSession::OnRepairTimeout
+ * (normSession.cpp:4720-4750) with NormObject::TxReset / ActivateRepairs (normObject.cpp:388-537)
+ * and NormBlock::TxReset (normSegment.cpp:219-259), and NextSenderMsg's end of block
+ * (normObject.cpp:2079-2083, ResetParityCount).  The call chain of a repair cycle is
+ *   nfec_tx_handle_nacks x N -> nfec_tx_activate_repairs -> nfec_tx_list -> nfec_tx_emit ->
+ *   nfec_tx_end_blocks.
+ * Every block of the batch counts as held by the sender: it has a NormBlock and its parity exists
+ * (the situation after nfec_encode).  Out of scope: the hold-off arm (TxUpdate against the transmit
+ * index), several objects per call, SenderRecoverBlock, the stream's LockBlocks / LockSegments,
+ * squelch, timers and CC feedback, and NORM_CMD(REPAIR_ADV).
+ *
+ * The state: caller-allocated arrays, device memory for the device entries, host memory for the
+ * *_host entries.  repair has the pending mask's layout.  TxInit is parity = {auto_parity, 0},
+ * everything else zero; TxRecover is parity = {m, m} (normSegment.h:106-129). */
+#define NFEC_TX_REPAIR_OBJECT 1u   /* an OBJECT-level request named the object (tx_repair_mask) */
+#define NFEC_TX_REPAIR_INFO   2u   /* repair_info                                                */
+#define NFEC_TX_PENDING_INFO  4u   /* pending_info, set by activation                            */
+typedef struct nfec_tx_repair_state {
+    uint32_t* repair;        /* [nblocks][mask_stride]: NormBlock::repair_mask                    */
+    uint16_t* parity;        /* [nblocks][2]: {parity_offset, parity_count}                       */
+    uint32_t* block_repair;  /* [(nblocks + 31) / 32]: NormObject::repair_mask, one bit per block */
+    uint32_t* object;        /* [1]: NFEC_TX_REPAIR_OBJECT | NFEC_TX_REPAIR_INFO | NFEC_TX_PENDING_INFO */
+} nfec_tx_repair_state;
+
+/* SenderHandleNackMessage, !holdoff, for one object.  Message i of nacks is the repair-request
+ * content payloads[offsets[i], offsets[i] + length[i]) of one NORM_NACK, at any byte alignment;
+ * count_dev is honoured.  A message that does not lie inside payload_bytes is unreadable: it is
+ * counted and no byte of it is loaded.  Every load is an aligned chunk of at most 16 bytes that
+ * holds at least one byte of the message (nfec_rx_ingest's rule).
+ *
+ * Order is part of the rule: the messages are handled in index order and each message's requests
+ * and items in their order in the bytes; the call behaves exactly as if one thread did that.
+ *
+ * A message is parsed as nfec_repair_parse_host parses it.  Where the parser stops the message
+ * ends: the units before the stop stand and the message is counted as cut short (a message whose
+ * last request is followed by fewer than 4 bytes is cut short too).  The level of a request comes
+ * from its flags in the reference's order (normSession.cpp:3763-3784): SEGMENT (0x01), else BLOCK
+ * (0x02), else OBJECT (0x08), else INFO (0x04); a request with none of them is skipped (its units
+ * are counted as ignored and change nothing, not even the stretch below).  A unit is (first,
+ * last); in an ITEMS request last = first.  The block of the batch of an item is (block id -
+ * first_block_id) mod 2^bits, as in nfec_rx_ingest.
+ *   - Foreign object.  A SEGMENT- or BLOCK-level unit whose first item names another object id is
+ *     ignored (the squelch is the caller's).  An OBJECT- or INFO-level unit is of this object when
+ *     (object_id - first.obj) mod 2^16 <= (last.obj - first.obj) mod 2^16, else foreign.
+ *   - INFO flag.  A unit of this object in a request that carries INFO sets NFEC_TX_REPAIR_INFO.
+ *     (A stated simplification: the reference looks at the first unit of an object's stretch only;
+ *     receivers put the flag on every request or on none.)
+ *   - OBJECT level sets NFEC_TX_REPAIR_OBJECT; INFO level does nothing beyond the INFO flag.
+ *   - BLOCK level (HandleBlockRequest): with b0, b1 the blocks of first and last, sets the
+ *     block_repair bits of [b0, min(b1, nblocks - 1)]; nothing when b0 > b1 or b0 >= nblocks.
+ *   - SEGMENT level, block b of first (last's block is not looked at, as in the reference).  The
+ *     unit is not applied when b >= nblocks, when nd_b is outside [1, k], when last.symbol <
+ *     first.symbol (the reference would add a wrapped count; no receiver sends it), or when the
+ *     unit is fresh and b's block_repair bit is set at that moment (IsRepairSet, :4048).  A unit
+ *     is fresh unless the previous SEGMENT-level unit of this message was applied and was for the
+ *     same block; a foreign unit of any level in between also makes the next one fresh
+ *     (freshObject), BLOCK-, OBJECT- and INFO-level units of this object in between do not.  A
+ *     unit that continues a stretch is not tested against block_repair again.  An applied unit's
+ *     erasure count is E = extra_parity + the widths (last.symbol - first.symbol + 1) of the
+ *     applied units of its stretch up to and including itself, in 32 bits.  It then runs
+ *     NormBlock::HandleSegmentRequest(first.symbol, last.symbol, nd_b, m, E) (normSegment.cpp:
+ *     341-402) on the block's parity pair {o, c} and repair mask:
+ *       first.symbol < nd_b:  o = c = m, and the slots [first, last] are set;
+ *       else, with avail = m - o:
+ *         E <= avail:  when E > c the slots [nd_b + o + c, nd_b + o + E) are set and c = E;
+ *         E >  avail:  when c < avail the slots [nd_b + o + c, nd_b + m) are set, c = avail and
+ *                      first += avail; then the slots [first, last] are set (the branch the
+ *                      reference marks "TBD").
+ *     Bits at or past nd_b + m are never set.
+ * unit_capacity bounds the units of the call (totals[0]); workspace is device memory, 16-byte
+ * aligned, of at least nfec_tx_nack_workspace_bytes(unit_capacity, count, nblocks) bytes.  When the
+ * call's units exceed unit_capacity no state is changed and totals = {units, 0, 0, 0, cut short,
+ * unreadable}: the caller repeats the call with more room.  Otherwise totals (device uint64 [6]) =
+ * {units in all, SEGMENT units applied, SEGMENT units not applied plus units ignored (foreign, or
+ * of a request without a level), block_repair bits newly set, messages cut short, messages
+ * unreadable}.  The result does not depend on the order in which the device's atomics land.
+ *
+ * Asynchronous on stream, on the codec device that holds state->repair; owns no codec state.  The
+ * pending mask is not an argument: handling never touches it.  NFEC_EINVAL for a fec_id / fec_m pair
+ * nfec_payload_id_read refuses and for fec_id 0, for null arrays, a mask_stride below (k + m + 31)
+ * / 32, a workspace that is null, misaligned or below the query's size, and extra_parity > 65535.
+ * count == 0 or nblocks == 0 is NFEC_OK with zero totals. */
+int nfec_tx_handle_nacks(const nfec_codec* codec, const nfec_rx_messages* nacks, uint8_t fec_id, uint8_t fec_m,
+                         uint16_t object_id, uint32_t first_block_id, const uint16_t* num_data, uint32_t nblocks,
+                         uint32_t mask_stride, uint32_t extra_parity, const nfec_tx_repair_state* state,
+                         uint32_t unit_capacity, void* workspace, uint64_t workspace_bytes,
+                         uint64_t* totals /* device [6] */, void* stream);
+/* (count does not enter the size today; pass nacks->count) */
+uint64_t nfec_tx_nack_workspace_bytes(uint32_t unit_capacity, uint32_t count, uint32_t nblocks);
+/* nfec_tx_handle_nacks' rule on host arrays (nacks' arrays, num_data, state and totals in host
+ * memory): no codec, no GPU, no workspace.  Also NFEC_EINVAL for k or m of 0 and k + m > 65536. */
+int nfec_tx_handle_nacks_host(uint32_t k, uint32_t m, const nfec_rx_messages* nacks, uint8_t fec_id, uint8_t fec_m,
+                              uint16_t object_id, uint32_t first_block_id, const uint16_t* num_data,
+                              uint32_t nblocks, uint32_t mask_stride, uint32_t extra_parity,
+                              const nfec_tx_repair_state* state, uint32_t unit_capacity, uint64_t* totals);
+
+/* OnRepairTimeout for the object (normSession.cpp:4720-4750): what the handled NACKs of a cycle
+ * left in the state goes into the pending mask.  Block TxReset (normSegment.cpp:219-259): the
+ * block's repair bits of [0, nd_b + m) become zero in every case; when pending over [0, nd_b + m)
+ * differs from the bits [0, nd_b + auto_parity), pending over [0, nd_b + m) becomes exactly those
+ * bits and parity becomes {auto_parity, m} (a reset "with a change").
+ *   With NFEC_TX_REPAIR_OBJECT set (NormObject::TxReset): every block is TxReset; nothing else of
+ *   the blocks' repair masks is activated.
+ *   Otherwise (NormObject::ActivateRepairs): every block whose block_repair bit is set is TxReset;
+ *   then for every block pending |= repair and repair = 0, over [0, nd_b + m).
+ * In both cases block_repair is cleared, and in the object word NFEC_TX_REPAIR_INFO moves to
+ * NFEC_TX_PENDING_INFO, NFEC_TX_REPAIR_OBJECT is cleared, and NFEC_TX_PENDING_INFO is also set when
+ * any block's TxReset changed something (NormObject::TxReset sets pending_info only when the object
+ * has NORM_INFO or the FTI travels in it, normObject.cpp:418-424: the caller masks the bit where
+ * neither holds).  Blocks with nd_b outside [1, k] are left alone.  totals (device uint64 [3]) =
+ * {blocks reset with a change, blocks whose segment repairs were activated, pending bits over all
+ * blocks after the call}.  Asynchronous on stream, on the codec device that holds pending.
+ * NFEC_EINVAL for null arrays, auto_parity > m and a mask_stride below (k + m + 31) / 32; nblocks ==
+ * 0 is NFEC_OK with zero totals and leaves the state alone. */
+int nfec_tx_activate_repairs(const nfec_codec* codec, const uint16_t* num_data, uint32_t nblocks, uint32_t auto_parity,
+                             uint32_t* pending, uint32_t mask_stride, const nfec_tx_repair_state* state,
+                             uint64_t* totals /* device [3] */, void* stream);
+int nfec_tx_activate_repairs_host(uint32_t k, uint32_t m, const uint16_t* num_data, uint32_t nblocks,
+                                  uint32_t auto_parity, uint32_t* pending, uint32_t mask_stride,
+                                  const nfec_tx_repair_state* state, uint64_t* totals);
+
+/* NextSenderMsg's end of block (normObject.cpp:2079-2083, ResetParityCount): for every block whose
+ * pending mask over [0, nd_b + m) is empty, parity_offset = min(parity_offset + parity_count, m)
+ * and parity_count = 0: the parity sent in this cycle is no longer fresh.  Idempotent.  The caller
+ * runs it after an emission (nfec_tx_emit with its pending argument) and before the next
+ * nfec_tx_handle_nacks; between a handle call and its activation it would be wrong, because the
+ * repairs handled so far count on the parity_count it clears.  Only state->parity is used and
+ * written.  Blocks with nd_b outside [1, k] are left alone.  Asynchronous on stream. */
+int nfec_tx_end_blocks(const nfec_codec* codec, const uint16_t* num_data, uint32_t nblocks, const uint32_t* pending,
+                       uint32_t mask_stride, const nfec_tx_repair_state* state, void* stream);
+int nfec_tx_end_blocks_host(uint32_t k, uint32_t m, const uint16_t* num_data, uint32_t nblocks,
+                            const uint32_t* pending, uint32_t mask_stride, const nfec_tx_repair_state* state);
 
 /* ---- object segmentation on the device ----
  * The mapping between a NORM data object (a contiguous run of bytes) and the source slots of its

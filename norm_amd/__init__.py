@@ -6,13 +6,15 @@ This package is the Python mirror of the reference's NormEncoder/NormDecoder plu
 surface (include/normEncoder.h:38-54) plus batch entry points for device-resident data.
 """
 from ._native import (NFEC_RS8, NFEC_RS16, NFEC_MDP, NFEC_ACCUMULATE, NFEC_FEATURE_RS16_TOEPLITZ,  # noqa: F401
-                      NFEC_STREAM_EOM, NFEC_STREAM_FLUSH, NFEC_STREAM_END, NFEC_NACK_INFO, NfecError, lib)
+                      NFEC_STREAM_EOM, NFEC_STREAM_FLUSH, NFEC_STREAM_END, NFEC_NACK_INFO, NFEC_TX_REPAIR_OBJECT, NFEC_TX_REPAIR_INFO,
+                      NFEC_TX_PENDING_INFO, NfecError, lib)
 from .codec import (  # noqa: F401
     NormEncoderRS8, NormDecoderRS8, NormEncoderRS16, NormDecoderRS16, NormEncoderMDP, NormDecoderMDP,
     BlockLayout, build_generator, device_count, fill_blocks, make_erasures, stream_copy, zero_erasures,
     received_mask, erasures_from_received_host, rx_parse_host, tx_list_host, rx_repair_requests_host,
     repair_parse_host, repair_max_units, repair_content_bound, object_layout, object_segment, object_block_sizes,
-    StreamState, stream_frame_host,
+    StreamState, stream_frame_host, TxRepairState, tx_repair_state, tx_handle_nacks_host, tx_activate_repairs_host,
+    tx_end_blocks_host,
 )
 
 __version__ = "0.1.0"

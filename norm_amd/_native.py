@@ -24,7 +24,9 @@ NFEC_NACK_INFO = 1
 # nfec_rx_repair_requests: a block's class, a request's form and flags
 NACK_SILENT, NACK_NEEDING, NACK_ABSENT = 0, 1, 2
 REPAIR_ITEMS, REPAIR_RANGES = 1, 2
-REPAIR_SEGMENT, REPAIR_BLOCK, REPAIR_INFO = 1, 2, 4
+REPAIR_SEGMENT, REPAIR_BLOCK, REPAIR_INFO, REPAIR_OBJECT = 1, 2, 4, 8
+# nfec_tx_repair_state: the object word
+NFEC_TX_REPAIR_OBJECT, NFEC_TX_REPAIR_INFO, NFEC_TX_PENDING_INFO = 1, 2, 4
 NFEC_FEATURE_RS16_TOEPLITZ, NFEC_FEATURE_RS16_TOEPLITZ2 = 1, 2
 NFEC_OPT_RS16_SHARED_TABLES, NFEC_OPT_RS16_TOEPLITZ_OFF, NFEC_OPT_RS16_TOEPLITZ_ON, NFEC_OPT_HOST_ONLY = 1, 2, 4, 8
 NFEC_OPT_RS16_TOEPLITZ_ONE_LEVEL = 16
@@ -76,6 +78,16 @@ class RxMessages(ctypes.Structure):
         ("length", ctypes.c_void_p),
         ("count", ctypes.c_uint32),
         ("count_dev", ctypes.c_void_p),
+    ]
+
+
+class TxRepairStateStruct(ctypes.Structure):
+    """nfec_tx_repair_state: the sender's repair state (device arrays, or host arrays for the *_host entries)."""
+    _fields_ = [
+        ("repair", ctypes.c_void_p),
+        ("parity", ctypes.c_void_p),
+        ("block_repair", ctypes.c_void_p),
+        ("object", ctypes.c_void_p),
     ]
 
 
@@ -240,6 +252,15 @@ _SIGS = {
     "nfec_tx_list_host": (_I, [_U32, _U32, _U32, _P, _U32, _P, _U32, _P, _U32, _U32, _P, _P, _P, _P, _U32, _P]),
     "nfec_tx_emit": (_I, [_P, ctypes.POINTER(BlockBatch), ctypes.POINTER(TxSegments), _U8, _U8, _U32, _P, _U32, _P,
                           _P]),
+    "nfec_tx_handle_nacks": (_I, [_P, ctypes.POINTER(RxMessages), _U8, _U8, _U16, _U32, _P, _U32, _U32, _U32,
+                                  ctypes.POINTER(TxRepairStateStruct), _U32, _P, _U64, _P, _P]),
+    "nfec_tx_nack_workspace_bytes": (_U64, [_U32, _U32, _U32]),
+    "nfec_tx_handle_nacks_host": (_I, [_U32, _U32, ctypes.POINTER(RxMessages), _U8, _U8, _U16, _U32, _P, _U32, _U32, _U32,
+                                       ctypes.POINTER(TxRepairStateStruct), _U32, _P]),
+    "nfec_tx_activate_repairs": (_I, [_P, _P, _U32, _U32, _P, _U32, ctypes.POINTER(TxRepairStateStruct), _P, _P]),
+    "nfec_tx_activate_repairs_host": (_I, [_U32, _U32, _P, _U32, _U32, _P, _U32, ctypes.POINTER(TxRepairStateStruct), _P]),
+    "nfec_tx_end_blocks": (_I, [_P, _P, _U32, _P, _U32, ctypes.POINTER(TxRepairStateStruct), _P]),
+    "nfec_tx_end_blocks_host": (_I, [_U32, _U32, _P, _U32, _P, _U32, ctypes.POINTER(TxRepairStateStruct)]),
     "nfec_object_layout_for": (_I, [_U64, _U32, _U32, ctypes.POINTER(ObjectLayout)]),
     "nfec_object_segment": (_I, [ctypes.POINTER(ObjectLayout), _U32, _U32, ctypes.POINTER(_U64), ctypes.POINTER(_U32)]),
     "nfec_object_block_sizes": (_I, [ctypes.POINTER(ObjectLayout), _U32, _U32, _P]),

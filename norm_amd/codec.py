@@ -394,6 +394,87 @@ class _Codec:
                                      pending.shape[1] if pending is not None else 0, _tensor_ptr(stats, "stats"),
                                      _stream_handle(stream)), "nfec_tx_emit")
 
+    # -- sender repair state on the device (nfec.h, "sender repair state on the device") --
+    def handle_nacks(self, state, payloads, offsets, length, num_data=None, fec_id=5, fec_m=8, object_id=0,
+                     first_block_id=0, extra_parity=0, unit_capacity=None, count_dev=None, workspace=None,
+                     totals=None, stream=None):
+        """The NACKs of a repair cycle into the sender's repair state (nfec_tx_handle_nacks:
+        SenderHandleNackMessage, !holdoff, for one object).  state: tx_repair_state(..., device=...);
+        payloads: the wire buffer, a uint8 tensor; message i is the repair-request content
+        payloads[offsets[i] : offsets[i] + length[i]] of one NORM_NACK (offsets int64, length int16,
+        handled in index order).  unit_capacity bounds the units of the call (default: what the
+        buffer's bytes could hold); when they exceed it nothing is changed.  workspace: a uint8
+        tensor of handle_nacks_workspace_bytes() bytes, or None.  Returns totals int64 [6] = (units,
+        SEGMENT units applied, units not applied or ignored, block_repair bits newly set, messages
+        cut short, messages unreadable)."""
+        import torch
+
+        self._need()
+        count = offsets.numel()
+        for t, size, what in ((offsets, 8, "offsets"), (length, 2, "length")):
+            if t.element_size() != size or t.numel() != count:
+                raise ValueError(f"{what} must hold {count} elements of {size} bytes")
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous CUDA (HIP) tensor")
+        if count_dev is not None and (count_dev.element_size() != 8 or count_dev.numel() < 1 or not count_dev.is_cuda):
+            raise ValueError("count_dev must be a 64-bit CUDA (HIP) tensor")
+        if payloads.element_size() != 1 or not payloads.is_cuda or not payloads.is_contiguous():
+            raise ValueError("payloads must be a contiguous uint8 CUDA (HIP) tensor")
+        nb = state.nblocks
+        if unit_capacity is None:
+            unit_capacity = payloads.numel() // 8 + 1
+        need = N.lib().nfec_tx_nack_workspace_bytes(unit_capacity, count, nb)
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.uint8, device=payloads.device)
+        if totals is None:
+            totals = torch.zeros(6, dtype=torch.int64, device=payloads.device)
+        msg = N.RxMessages()
+        msg.payloads = payloads.data_ptr() if payloads.numel() else None
+        msg.payload_bytes = payloads.numel()
+        msg.offsets, msg.length = offsets.data_ptr(), length.data_ptr()
+        msg.count = count
+        msg.count_dev = count_dev.data_ptr() if count_dev is not None else None
+        st = state.struct()
+        N.check(N.lib().nfec_tx_handle_nacks(self._h, ctypes.byref(msg), fec_id, fec_m, object_id & 0xFFFF,
+                                             first_block_id & 0xFFFFFFFF, _tensor_ptr(num_data, "num_data"), nb,
+                                             state.mask_stride, extra_parity, ctypes.byref(st), unit_capacity,
+                                             _tensor_ptr(workspace, "workspace"), workspace.numel(),
+                                             _tensor_ptr(totals, "totals"), _stream_handle(stream)),
+                "nfec_tx_handle_nacks")
+        return totals
+
+    def activate_repairs(self, state, pending, num_data=None, auto_parity=0, totals=None, stream=None):
+        """What the handled NACKs left in the repair state into the pending mask
+        (nfec_tx_activate_repairs: OnRepairTimeout for the object).  Returns totals int64 [3] = (blocks
+        reset with a change, blocks whose segment repairs were activated, pending bits after)."""
+        import torch
+
+        self._need()
+        _mask_check(pending, state.nblocks)
+        if pending.shape[1] != state.mask_stride:
+            raise ValueError("pending and state.repair must have one mask_stride")
+        if totals is None:
+            totals = torch.zeros(3, dtype=torch.int64, device=pending.device)
+        st = state.struct()
+        N.check(N.lib().nfec_tx_activate_repairs(self._h, _tensor_ptr(num_data, "num_data"), state.nblocks, auto_parity,
+                                                 _tensor_ptr(pending, "pending"), state.mask_stride, ctypes.byref(st),
+                                                 _tensor_ptr(totals, "totals"), _stream_handle(stream)),
+                "nfec_tx_activate_repairs")
+        return totals
+
+    def end_blocks(self, state, pending, num_data=None, stream=None):
+        """NextSenderMsg's end of block (nfec_tx_end_blocks): a block whose pending mask is empty
+        moves its parity_count into its parity_offset.  After emit_segments, before the next
+        handle_nacks."""
+        self._need()
+        _mask_check(pending, state.nblocks)
+        if pending.shape[1] != state.mask_stride:
+            raise ValueError("pending and state.repair must have one mask_stride")
+        st = state.struct()
+        N.check(N.lib().nfec_tx_end_blocks(self._h, _tensor_ptr(num_data, "num_data"), state.nblocks,
+                                           _tensor_ptr(pending, "pending"), state.mask_stride, ctypes.byref(st),
+                                           _stream_handle(stream)), "nfec_tx_end_blocks")
+
     # -- object segmentation on the device (nfec.h, "object segmentation on the device") --
     def _object_call(self, obj, layout, blocks):
         self._need()
@@ -909,6 +990,153 @@ def repair_parse_host(fec_id, fec_m, content, capacity=None):
                                                ctypes.byref(consumed)), "nfec_repair_parse_host")
     n = min(n, capacity)
     return flags[:n], form[:n], first[:n], last[:n], consumed.value
+
+
+class TxRepairState:
+    """nfec_tx_repair_state: the sender's repair state of one object's batch.  repair 32-bit
+    [nblocks, mask_stride], parity 16-bit [nblocks, 2] = (parity_offset, parity_count), block_repair
+    32-bit [max(1, (nblocks + 31) // 32)], object 32-bit [1]: torch tensors on a device, or NumPy
+    arrays for the *_host functions."""
+
+    FIELDS = ("repair", "parity", "block_repair", "object")
+
+    def __init__(self, repair, parity, block_repair, object):
+        self.repair, self.parity, self.block_repair, self.object = repair, parity, block_repair, object
+
+    @property
+    def nblocks(self):
+        return self.repair.shape[0]
+
+    @property
+    def mask_stride(self):
+        return self.repair.shape[1]
+
+    @property
+    def on_host(self):
+        return not hasattr(self.repair, "is_cuda")
+
+    def arrays(self):
+        return tuple(getattr(self, f) for f in self.FIELDS)
+
+    def struct(self):
+        st = N.TxRepairStateStruct()
+        for f in self.FIELDS:
+            t = getattr(self, f)
+            if self.on_host:
+                if not t.flags["C_CONTIGUOUS"]:
+                    raise ValueError(f"state.{f} must be contiguous")
+                setattr(st, f, t.ctypes.data)
+            else:
+                if not t.is_cuda or not t.is_contiguous():
+                    raise ValueError(f"state.{f} must be a contiguous CUDA (HIP) tensor")
+                setattr(st, f, t.data_ptr())
+        return st
+
+    def clone(self):
+        return TxRepairState(*(t.copy() if self.on_host else t.clone() for t in self.arrays()))
+
+    def to_host(self):
+        """The state as NumPy arrays (uint32 / uint16), a copy."""
+        import numpy as np
+
+        if self.on_host:
+            return self.clone()
+        out = [t.cpu().numpy() for t in self.arrays()]
+        return TxRepairState(out[0].view(np.uint32), out[1].view(np.uint16), out[2].view(np.uint32), out[3].view(np.uint32))
+
+    def to_device(self, device="cuda"):
+        import numpy as np
+        import torch
+
+        src = self.to_host()
+        views = (src.repair.view(np.int32), src.parity.view(np.int16), src.block_repair.view(np.int32), src.object.view(np.int32))
+        return TxRepairState(*(torch.from_numpy(v.copy()).to(device) for v in views))
+
+
+def tx_repair_state(nblocks, k, m, auto_parity=0, device=None, mask_stride=None):
+    """The repair state NormBlock::TxInit leaves (parity = (auto_parity, 0), everything else zero) for
+    nblocks blocks of k + m slots: torch tensors on `device`, or NumPy arrays with device=None."""
+    import numpy as np
+
+    if not 0 <= auto_parity <= m:
+        raise ValueError("auto_parity must lie in [0, m]")
+    stride = (k + m + 31) // 32 if mask_stride is None else mask_stride
+    parity = np.zeros((nblocks, 2), np.uint16)
+    parity[:, 0] = auto_parity
+    state = TxRepairState(np.zeros((nblocks, stride), np.uint32), parity, np.zeros(max(1, (nblocks + 31) // 32), np.uint32),
+                          np.zeros(1, np.uint32))
+    return state if device is None else state.to_device(device)
+
+
+def _host_state(state, pending=None):
+    import numpy as np
+
+    if not state.on_host:
+        raise ValueError("state must hold NumPy arrays (tx_repair_state(..., device=None))")
+    want = (np.uint32, np.uint16, np.uint32, np.uint32)
+    for f, dt in zip(state.FIELDS, want):
+        if getattr(state, f).dtype != dt:
+            raise ValueError(f"state.{f} must be {np.dtype(dt).name}")
+    if pending is not None and (pending.dtype != np.uint32 or pending.ndim != 2 or pending.shape != state.repair.shape
+                                or not pending.flags["C_CONTIGUOUS"]):
+        raise ValueError("pending must be a contiguous uint32 array of state.repair's shape")
+    return state.struct()
+
+
+def tx_handle_nacks_host(k, m, state, payloads, offsets, length, num_data=None, fec_id=5, fec_m=8, object_id=0,
+                         first_block_id=0, extra_parity=0, unit_capacity=None, count=None, payload_bytes=None):
+    """nfec_tx_handle_nacks_host: Codec.handle_nacks on host arrays (no GPU), in place on `state`.
+    payloads: NumPy uint8 array; offsets / length: one entry per message; count: what count_dev would
+    hold, or None; payload_bytes: the wire buffer's size when it is not payloads.size.  Returns totals
+    uint64 [6]."""
+    import numpy as np
+
+    wire = np.ascontiguousarray(payloads).view(np.uint8).reshape(-1)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    ln = np.ascontiguousarray(length, dtype=np.uint16)
+    if off.size != ln.size:
+        raise ValueError("offsets and length must hold one entry per message")
+    nd = None if num_data is None else np.ascontiguousarray(num_data, dtype=np.uint16)
+    st = _host_state(state)
+    unit_capacity = wire.size // 8 + 1 if unit_capacity is None else unit_capacity
+    count_dev = None if count is None else np.array([count], np.uint64)
+    msg = N.RxMessages()
+    msg.payloads = wire.ctypes.data if wire.size else None
+    msg.payload_bytes = wire.size if payload_bytes is None else payload_bytes
+    msg.offsets, msg.length = off.ctypes.data, ln.ctypes.data
+    msg.count = off.size
+    msg.count_dev = None if count_dev is None else count_dev.ctypes.data
+    totals = np.zeros(6, np.uint64)
+    N.check(N.lib().nfec_tx_handle_nacks_host(k, m, ctypes.byref(msg), fec_id, fec_m, object_id & 0xFFFF,
+                                              first_block_id & 0xFFFFFFFF, None if nd is None else nd.ctypes.data,
+                                              state.nblocks, state.mask_stride, extra_parity, ctypes.byref(st),
+                                              unit_capacity, totals.ctypes.data), "nfec_tx_handle_nacks_host")
+    return totals
+
+
+def tx_activate_repairs_host(k, m, state, pending, num_data=None, auto_parity=0):
+    """nfec_tx_activate_repairs_host: Codec.activate_repairs on host arrays, in place on `state` and
+    `pending` (uint32 [nblocks, mask_stride]).  Returns totals uint64 [3]."""
+    import numpy as np
+
+    st = _host_state(state, pending)
+    nd = None if num_data is None else np.ascontiguousarray(num_data, dtype=np.uint16)
+    totals = np.zeros(3, np.uint64)
+    N.check(N.lib().nfec_tx_activate_repairs_host(k, m, None if nd is None else nd.ctypes.data, state.nblocks, auto_parity,
+                                                  pending.ctypes.data, state.mask_stride, ctypes.byref(st),
+                                                  totals.ctypes.data), "nfec_tx_activate_repairs_host")
+    return totals
+
+
+def tx_end_blocks_host(k, m, state, pending, num_data=None):
+    """nfec_tx_end_blocks_host: Codec.end_blocks on host arrays, in place on state.parity."""
+    import numpy as np
+
+    st = _host_state(state, pending)
+    nd = None if num_data is None else np.ascontiguousarray(num_data, dtype=np.uint16)
+    N.check(N.lib().nfec_tx_end_blocks_host(k, m, None if nd is None else nd.ctypes.data, state.nblocks,
+                                            pending.ctypes.data, state.mask_stride, ctypes.byref(st)),
+            "nfec_tx_end_blocks_host")
 
 
 def tx_list_host(k, m, vector_size, pending, num_data=None, seg_length=None, gap=0, capacity=None):

@@ -866,6 +866,111 @@ int nfec_rx_repair_requests(const nfec_codec* codec, const uint32_t* received, u
     return launch_nack(a, static_cast<hipStream_t>(stream));
 }
 
+// ---- sender repair state on the device (kernels_txrepair.hip) ----
+static TxRepairState repair_state_view(const nfec_tx_repair_state* state)
+{
+    TxRepairState v;
+    v.repair = state->repair, v.parity = state->parity, v.block_repair = state->block_repair, v.object = state->object;
+    return v;
+}
+
+uint64_t nfec_tx_nack_workspace_bytes(uint32_t unit_capacity, uint32_t count, uint32_t nblocks)
+{
+    return tx_nack_workspace_bytes(unit_capacity, nblocks);
+}
+
+int nfec_tx_handle_nacks(const nfec_codec* codec, const nfec_rx_messages* nacks, uint8_t fec_id, uint8_t fec_m,
+                         uint16_t object_id, uint32_t first_block_id, const uint16_t* num_data, uint32_t nblocks,
+                         uint32_t mask_stride, uint32_t extra_parity, const nfec_tx_repair_state* state,
+                         uint32_t unit_capacity, void* workspace, uint64_t workspace_bytes, uint64_t* totals, void* stream)
+{
+    if (!codec) return fail(NFEC_EINVAL, "null codec");
+    uint32_t id_kind = 0;
+    int rc = tx_nack_check(nacks, fec_id, fec_m, extra_parity, totals, &id_kind);
+    if (rc || (rc = tx_repair_check(codec->k, codec->m, nblocks, mask_stride, state, "tx_handle_nacks"))) return rc;
+    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15u))
+        return fail(NFEC_EINVAL, "tx_handle_nacks: workspace is null or not 16-byte aligned");
+    if (workspace_bytes < tx_nack_workspace_bytes(unit_capacity, nblocks))
+        return fail(NFEC_EINVAL, "tx_handle_nacks: workspace smaller than nfec_tx_nack_workspace_bytes");
+    if (primary(codec)->host_only) return host_only_fail();
+    const nfec_codec* c = stripe_for(const_cast<nfec_codec*>(codec), nblocks ? (const void*)state->repair : totals);
+    if (!c) return fail(NFEC_EINVAL, "repair state is not on a device of the codec");
+    DeviceGuard g(c->device);
+    TxNackArgs a;
+    a.payloads = static_cast<const uint8_t*>(nacks->payloads);
+    a.payload_bytes = nacks->payload_bytes;
+    a.offsets = nacks->offsets;
+    a.length = nacks->length;
+    a.count = nacks->count;
+    a.count_dev = nacks->count_dev;
+    a.id_kind = id_kind;
+    a.fec_id = fec_id;
+    a.object_id = object_id;
+    a.first_block_id = first_block_id;
+    a.num_data = num_data;
+    a.k = c->k;
+    a.m = c->m;
+    a.nblocks = nblocks;
+    a.mask_stride = mask_stride;
+    a.extra_parity = extra_parity;
+    a.state = repair_state_view(state);
+    a.unit_capacity = unit_capacity;
+    a.workspace = static_cast<uint8_t*>(workspace);
+    a.totals = totals;
+    return launch_tx_handle_nacks(a, static_cast<hipStream_t>(stream));
+}
+
+static int tx_activate_args(const nfec_codec* codec, const uint16_t* num_data, uint32_t nblocks, uint32_t auto_parity,
+                            const uint32_t* pending, uint32_t mask_stride, const nfec_tx_repair_state* state,
+                            const void* anchor, const char* what, TxActivateArgs* a, int* device)
+{
+    if (!codec) return fail(NFEC_EINVAL, "null codec");
+    int rc = tx_repair_check(codec->k, codec->m, nblocks, mask_stride, state, what);
+    if (rc) return rc;
+    if (nblocks && !pending) return fail(NFEC_EINVAL, std::string(what) + ": null pending mask");
+    if (auto_parity > codec->m) return fail(NFEC_EINVAL, std::string(what) + ": auto_parity above m");
+    if (primary(codec)->host_only) return host_only_fail();
+    if (nblocks == 0 && !anchor) return NFEC_OK;  // (nothing to launch, nothing to place on a device)
+    const nfec_codec* c = stripe_for(const_cast<nfec_codec*>(codec), nblocks ? (const void*)pending : anchor);
+    if (!c) return fail(NFEC_EINVAL, "pending mask is not on a device of the codec");
+    a->num_data = num_data;
+    a->k = c->k;
+    a->m = c->m;
+    a->nblocks = nblocks;
+    a->auto_parity = auto_parity;
+    a->pending = const_cast<uint32_t*>(pending);
+    a->mask_stride = mask_stride;
+    a->state = repair_state_view(state);
+    *device = c->device;
+    return NFEC_OK;
+}
+
+int nfec_tx_activate_repairs(const nfec_codec* codec, const uint16_t* num_data, uint32_t nblocks, uint32_t auto_parity,
+                             uint32_t* pending, uint32_t mask_stride, const nfec_tx_repair_state* state, uint64_t* totals,
+                             void* stream)
+{
+    if (!totals) return fail(NFEC_EINVAL, "tx_activate_repairs: null totals");
+    TxActivateArgs a;
+    int device = 0;
+    int rc = tx_activate_args(codec, num_data, nblocks, auto_parity, pending, mask_stride, state, totals, "tx_activate_repairs",
+                              &a, &device);
+    if (rc) return rc;
+    DeviceGuard g(device);
+    a.totals = totals;
+    return launch_tx_activate_repairs(a, static_cast<hipStream_t>(stream));
+}
+
+int nfec_tx_end_blocks(const nfec_codec* codec, const uint16_t* num_data, uint32_t nblocks, const uint32_t* pending,
+                       uint32_t mask_stride, const nfec_tx_repair_state* state, void* stream)
+{
+    TxActivateArgs a;
+    int device = 0;
+    int rc = tx_activate_args(codec, num_data, nblocks, 0, pending, mask_stride, state, nullptr, "tx_end_blocks", &a, &device);
+    if (rc || nblocks == 0) return rc;
+    DeviceGuard g(device);
+    return launch_tx_end_blocks(a, static_cast<hipStream_t>(stream));
+}
+
 // ---- sender assembly on the device (kernels_tx.hip) ----
 // The argument-check order is the receiver entries': arguments first, then the codec's device.
 int nfec_tx_list(const nfec_codec* codec, const uint32_t* pending, uint32_t mask_stride, const uint16_t* num_data,

@@ -870,6 +870,57 @@ struct NackFormat;
 int nack_format(uint8_t fec_id, uint8_t fec_m, uint16_t object_id, uint32_t first_block_id, uint32_t flags,
                 uint32_t max_units, NackFormat* f);
 
+// Sender repair state on the device (kernels_txrepair.hip; nfec.h "sender repair state on the
+// device"; repair_layout.hpp holds the rule).  Handle: one wave per message walks its requests and
+// leaves every SEGMENT-level unit that can be applied as a keyed record on its block's list, every
+// BLOCK-level unit as the smallest key per covered block; then one wave per block orders its
+// records by key and applies them.  Activate and end of block: one wave per block, lanes over the
+// mask words.
+struct TxRepairState {
+    uint32_t* repair = nullptr;            // [nblocks][mask_stride]
+    uint16_t* parity = nullptr;            // [nblocks][2]
+    uint32_t* block_repair = nullptr;      // [(nblocks + 31) / 32]
+    uint32_t* object = nullptr;            // [1]
+};
+struct TxNackArgs {
+    const uint8_t* payloads = nullptr;     // the wire buffer
+    uint64_t payload_bytes = 0;
+    const uint64_t* offsets = nullptr;
+    const uint16_t* length = nullptr;
+    uint32_t count = 0;
+    const uint64_t* count_dev = nullptr;   // device, or null: min(count, *count_dev) messages
+    uint32_t id_kind = 0;                  // the payload ID's layout (PAYLOAD_ID_*, rx_parse.hpp)
+    uint32_t fec_id = 0, object_id = 0, first_block_id = 0;
+    const uint16_t* num_data = nullptr;    // per block, or null = k
+    uint32_t k = 0, m = 0;
+    uint32_t nblocks = 0;
+    uint32_t mask_stride = 0;
+    uint32_t extra_parity = 0;
+    TxRepairState state;
+    uint32_t unit_capacity = 0;
+    uint8_t* workspace = nullptr;          // tx_nack_workspace_bytes(unit_capacity, nblocks), 16-byte aligned
+    uint64_t* totals = nullptr;            // [6]
+};
+uint64_t tx_nack_workspace_bytes(uint32_t unit_capacity, uint32_t nblocks);
+int launch_tx_handle_nacks(const TxNackArgs& a, hipStream_t s);
+struct TxActivateArgs {
+    const uint16_t* num_data = nullptr;    // per block, or null = k
+    uint32_t k = 0, m = 0;
+    uint32_t nblocks = 0;
+    uint32_t auto_parity = 0;
+    uint32_t* pending = nullptr;           // [nblocks][mask_stride]; end of block only reads it
+    uint32_t mask_stride = 0;
+    TxRepairState state;
+    uint64_t* totals = nullptr;            // [3] (activation)
+};
+int launch_tx_activate_repairs(const TxActivateArgs& a, hipStream_t s);
+int launch_tx_end_blocks(const TxActivateArgs& a, hipStream_t s);
+// the argument checks the device and the host entries share (tx_repair_host.cpp)
+int tx_repair_check(uint32_t k, uint32_t m, uint32_t nblocks, uint32_t mask_stride, const nfec_tx_repair_state* state,
+                    const char* what);
+int tx_nack_check(const nfec_rx_messages* nacks, uint8_t fec_id, uint8_t fec_m, uint32_t extra_parity, const uint64_t* totals,
+                  uint32_t* id_kind);
+
 // Object segmentation on the device (kernels_obj.hip; nfec.h "object segmentation on the device").
 // One workgroup per run of up to 64 consecutive segments of a block; its lanes stride over the
 // run's (segment, 16-byte piece) pairs as one flat index.  Read: the object's bytes, at any

@@ -641,6 +641,7 @@ FdecArgs fdec_args(nfec_codec* c, const nfec_block_batch* b, const DecodeRoute& 
     a.accumulate = accumulates(b);
     a.num_data = p.nd;
     a.lane_major = r.lane_major;
+    a.xcd_remap = bs_flags() & 1u;
     return a;
 }
 

@@ -591,6 +591,7 @@ struct FdecArgs {
     uint32_t accumulate = 0;
     uint32_t lane_major = 0;             // lane L holds items 4L..4L+3; lanes without one exit
     const uint16_t* num_data = nullptr;  // per block (null: k): parity row t read at slot numData + t
+    uint32_t xcd_remap = 0;              // the generator's xcd option: each XCD a contiguous range of blocks (bs::wg_index)
 };
 int launch_rs8_fused_decode(uint32_t k, uint32_t m, const FdecArgs& a, hipStream_t s);
 bool rs8_fused_decode_covers(uint32_t k, uint32_t m, const FdecArgs& a);

@@ -393,10 +393,11 @@ def gen_kernel(k, m, probe=None):
     body = "\\n\"\n        \"".join(asm)
     if probe == "persist":
         return persist_kernel(K, nr, body, k)
+    wg = "bs::wg_index(a.xcd_remap)" if F3_PRODUCT["xcd"] else "blockIdx.x"
     return f"""__global__ __launch_bounds__(256, 2) void {K}(FdecArgs a)
 {{
     const uint32_t lane = threadIdx.x & 63;
-    const uint32_t blk = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    const uint32_t blk = __builtin_amdgcn_readfirstlane({wg} * 4 + (threadIdx.x >> 6));
     if (blk >= a.nblocks) return;
 {dephase}    const int32_t rows = (int32_t)__builtin_amdgcn_readfirstlane((uint32_t)a.rows[blk]);
     const uint32_t ps0 = __builtin_amdgcn_readfirstlane(a.psel[2 * (uint64_t)blk]);
@@ -475,6 +476,13 @@ F3_PARK = 8 * (F3_MAX_VEC // 32)           # bytes of one parked plane pair: 8 p
 # NFEC_FDEC_VARIANT ids (diagnostic library, with NFEC_FDEC3=0 so that the batch reaches
 # launch_rs8_fused_decode): fdec3's own probes (no solve / DMA, waits and LDS reads only / no DMA)
 F3_PROBES = {10: "nos2", 11: "nos1", 12: "noload"}
+# ... and the stream variants (F3_FLAGS), each as the whole kernel and as its load-only probe
+# ("dfs": the stores at the default policy, the stream before round 20 made them non-temporal)
+F3_VARIANTS = {20: (("xcd",), None), 21: (("xcd",), "nos1"), 22: (("ntl",), None), 23: (("ntl",), "nos1"),
+               24: (("dfs",), None), 25: (("dfs",), "nos1"), 26: (("pair",), None), 27: (("pair",), "nos1"),
+               28: (("quad",), None), 29: (("quad",), "nos1"), 30: (("xcd", "pair"), None), 31: (("xcd", "pair"), "nos1"),
+               34: (("sc1s",), None), 35: (("sc1s",), "nos1"), 36: (("sc1l",), None), 37: (("sc1l",), "nos1"),
+               38: (("sysnts",), None), 39: (("sysnts",), "nos1")}
 assert 4 * F3_WAVE_LDS <= F3_LDS_BUDGET and F3_WAVE_LDS % 16 == 0
 
 
@@ -522,7 +530,26 @@ def f3_temps(regs):
     return make
 
 
-def fdec3_stage1(k, m, probe=None):
+# Generator options of the fdec3 stream (profiles/r20/dma_stream).  F3_PRODUCT
+# is what rs8_fdec3.hip is generated with; the diagnostic library builds the others as variants:
+#   xcd     workgroup -> block through bs::wg_index(a.xcd_remap): each XCD a contiguous block range
+#   lpol    cache-policy suffix of the column DMA (" nt"), spol: of the repaired-row stores
+#   refill  columns re-armed together: 1 = one slot per step; R = R adjacent columns (contiguous in
+#           memory when seg_stride == vec) back to back at every R-th step, R slots at a time
+F3_PRODUCT = {"xcd": False, "lpol": "", "spol": " nt", "refill": 1}
+F3_FLAGS = {"xcd": {"xcd": True}, "ntl": {"lpol": " nt"}, "dfs": {"spol": ""},
+            "pair": {"refill": 2}, "quad": {"refill": 4},
+            "sc1l": {"lpol": " sc1"}, "sc1s": {"spol": " sc1"}, "sysnts": {"spol": " sc0 sc1 nt"}}
+
+
+def f3_opt(flags=()):
+    opt = dict(F3_PRODUCT)
+    for f in flags:
+        opt.update(F3_FLAGS[f])
+    return opt
+
+
+def fdec3_stage1(k, m, probe=None, opt=None):
     """z rows 0..15 into f3_acc.  The arithmetic is fdec_asm's; a column comes HBM -> LDS by two
     buffer_load_dwordx4 ... lds pieces (lanes 0..63 bytes 0..1023, the rest at offset 1024, EXEC
     widened to the piece's lanes) through a descriptor that starts at the segment and has vec
@@ -530,10 +557,15 @@ def fdec3_stage1(k, m, probe=None):
     the last piece of a 1,400-byte segment is half inside it and reads nothing past it.  16-byte
     pieces from 8-byte aligned segments: buffer loads need dword alignment only.
     Ordering, all within the wave: a slot is read (ds_read_b64) after the counted vmcnt that
-    retires its DMA, and re-armed after the lgkmcnt(0) that returned its reads."""
+    retires its DMA, and re-armed after the lgkmcnt(0) that returned its reads.  With refill R > 1
+    the slots of columns c - R + 1 .. c are re-armed together behind column c's lgkmcnt(0), c = R - 1
+    (mod R); every vmcnt still follows from the last column issued."""
+    opt = opt or F3_PRODUCT
+    R, lpol = opt["refill"], opt["lpol"]
     G = generator(k, m)
     nr = min(NCOLS_PAR, m)
     ncol = k + nr
+    assert F3_NSLOT % R == 0 and ncol % R == 0 and R < F3_NSLOT
     L = [f"s_mov_b64 s[{S3_EX}:{S3_EX + 1}], exec",
          f"s_mov_b64 s[{S3_BASE}:{S3_BASE + 1}], %[base]",
          f"s_mov_b32 s{S_LRS + 3}, 0x00020000", f"s_mov_b32 s{S_SRS + 3}, 0x00020000",
@@ -557,9 +589,9 @@ def fdec3_stage1(k, m, probe=None):
         out += [f"s_add_u32 s{S_LRS}, s{S3_BASE}, s{S_COL}", f"s_addc_u32 s{S_LRS + 1}, s{S3_BASE + 1}, 0",
                 f"s_add_u32 m0, %[wb], {(c % F3_NSLOT) * F3_SLOT}",
                 "s_mov_b64 exec, %[dm0]",
-                f"buffer_load_dwordx4 %[dma], s[{S_LRS}:{S_LRS + 3}], 0 offen lds",
+                f"buffer_load_dwordx4 %[dma], s[{S_LRS}:{S_LRS + 3}], 0 offen{lpol} lds",
                 "s_mov_b64 exec, %[dm1]",
-                f"buffer_load_dwordx4 %[dma], s[{S_LRS}:{S_LRS + 3}], 0 offen offset:1024 lds",
+                f"buffer_load_dwordx4 %[dma], s[{S_LRS}:{S_LRS + 3}], 0 offen offset:1024{lpol} lds",
                 "s_mov_b64 exec, %[live]"]
         return out
 
@@ -587,8 +619,9 @@ def fdec3_stage1(k, m, probe=None):
     for c in range(ncol):
         w, other = f3_set(c % 2), f3_set((c + 1) % 2)
         L.append("s_waitcnt lgkmcnt(0)")  # column c is in its set (and slot c % F3_NSLOT is free)
-        if c + F3_NSLOT < ncol:
-            L += dma(c + F3_NSLOT)
+        if c % R == R - 1 and c + F3_NSLOT < ncol:
+            for n in range(c + F3_NSLOT - R + 1, c + F3_NSLOT + 1):
+                L += dma(n)
             issued = c + F3_NSLOT
         if probe != "noload" and c + 1 < ncol:
             L.append(f"s_waitcnt vmcnt({2 * (issued - c - 1)})")
@@ -635,13 +668,14 @@ def fdec3_stage1(k, m, probe=None):
     return L
 
 
-def fdec3_stage2(e16, probe=None):
+def fdec3_stage2(e16, probe=None, opt=None):
     """fdec_asm's solve with z rows 8..15 parked in the wave's LDS region (the ring is dead: every
     DMA retired, every read returned) and the d accumulators in their registers.  Row t's planes
     reach the window by v_mov, from the row's registers (t < 8) or from the staging set, which a
     parked row's four ds_read_b64 fill one row ahead, behind the previous row's calls.  The store
     offsets are recomputed per half; the store descriptor starts at the output's segment and has
     vec records, so items past the segment are dropped by the range check."""
+    spol = (opt or F3_PRODUCT)["spol"] or SPOL
     win, stg = f3_set(0), f3_set(1)
     so = [f3_combo(0, a) for a in MULTI[:4]]
     free = [f3_combo(g, a) for a in MULTI for g in (0, 1) if f3_combo(g, a) not in so]
@@ -721,7 +755,7 @@ def fdec3_stage2(e16, probe=None):
                     S.append(f"v_xor_b32 v{w[2 * q + 1]}, v{win[2 * q + 1]}, v{w[2 * q + 1]}")
                 S.append(f"Lna{s}{x}_%=:")
                 for q in range(4):
-                    S.append(f"buffer_store_dwordx2 v[{w[2 * q]}:{w[2 * q + 1]}], v{so[q]}, s[{S_SRS}:{S_SRS + 3}], 0 offen{SPOL}")
+                    S.append(f"buffer_store_dwordx2 v[{w[2 * q]}:{w[2 * q + 1]}], v{so[q]}, s[{S_SRS}:{S_SRS + 3}], 0 offen{spol}")
             if h == 0:
                 S.append(f"Lhalf{h}{x}_%=:")
         return S
@@ -766,7 +800,7 @@ F3_FORMS = [
     ("WL", "s_waitcnt lgkmcnt({0})"),
     ("WV", "s_waitcnt vmcnt({0})"),
     ("BL", f"buffer_load_dwordx2 v[{{0}}:{{1}}], v{{2}}, s[{S_SRS}:{S_SRS + 3}], 0 offen"),
-    ("BS", f"buffer_store_dwordx2 v[{{0}}:{{1}}], v{{2}}, s[{S_SRS}:{S_SRS + 3}], 0 offen"),
+    ("BS", f"buffer_store_dwordx2 v[{{0}}:{{1}}], v{{2}}, s[{S_SRS}:{S_SRS + 3}], 0 offen{F3_PRODUCT['spol']}"),
 ]
 
 
@@ -861,12 +895,19 @@ def f3_clobbers():
     return ", ".join(v + s + ['"m0"', '"scc"', '"memory"'])
 
 
-def gen_kernel3(k, m, probe=None, compact=False):
+def f3_name(k, m, flags=(), probe=None):
+    """rs8_fdec3_*: the kernel and its probes; rs8_f3s_*: a stream variant (and its probe)"""
+    return (f"rs8_f3s_k{k}_m{m}_" + "_".join(flags) if flags else f"rs8_fdec3_k{k}_m{m}") + (f"_probe_{probe}" if probe else "")
+
+
+def gen_kernel3(k, m, probe=None, compact=False, flags=()):
     """the fdec3 kernel of (k, m), or one of its timing probes (diagnostic library; their
-    outputs are wrong on purpose)"""
-    K = f"rs8_fdec3_k{k}_m{m}" + (f"_probe_{probe}" if probe else "")
+    outputs are wrong on purpose); flags: the F3_FLAGS of a stream variant (diagnostic library)"""
+    K = f3_name(k, m, flags, probe)
     nr = min(NCOLS_PAR, m)
-    asm = fdec3_stage1(k, m, None if probe == "nos2" else probe) + fdec3_stage2(nr == 16, probe)
+    opt = f3_opt(flags)
+    asm = fdec3_stage1(k, m, None if probe == "nos2" else probe, opt) + fdec3_stage2(nr == 16, probe, opt)
+    wg = "bs::wg_index(a.xcd_remap)" if opt["xcd"] else "blockIdx.x"
     if compact:
         defs, packed = f3_compact(asm)
         body = "\n        ".join(packed)
@@ -877,7 +918,7 @@ def gen_kernel3(k, m, probe=None, compact=False):
     __shared__ __attribute__((aligned(16))) uint8_t ring[4 * {F3_WAVE_LDS}];
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t blk = blockIdx.x * 4 + wave;
+    const uint32_t blk = {wg} * 4 + wave;
     if (blk >= a.nblocks) return;
     const int32_t rows = (int32_t)__builtin_amdgcn_readfirstlane((uint32_t)a.rows[blk]);
     const uint32_t ps0 = __builtin_amdgcn_readfirstlane(a.psel[2 * (uint64_t)blk]);
@@ -936,6 +977,7 @@ def main_fdec3(path):
         "// in LDS during the solve; DESIGN.md section 4) for k = 64, m = 32 or 16.  The assembly is written",
         "// with one macro per instruction shape; each expands to the instruction's text.",
         '#include "nfec_internal.hpp"',
+    ] + (['#include "bitslice.hpp"'] if F3_PRODUCT["xcd"] else []) + [
         "",
         "namespace nfec {",
         "namespace {",
@@ -980,6 +1022,7 @@ def main():
         "// (k, m) in: " + ", ".join(f"({k},{m})" for k, m in shapes),
         "#include <cstdlib>",
         '#include "nfec_internal.hpp"',
+    ] + (['#include "bitslice.hpp"'] if diag or F3_PRODUCT["xcd"] else []) + [
         "",
         "namespace nfec {",
         "namespace {",
@@ -991,6 +1034,8 @@ def main():
                 parts.append(gen_kernel(k, m, probe))
             for probe in F3_PROBES.values():
                 parts.append(gen_kernel3(k, m, probe))
+            for flags, probe in F3_VARIANTS.values():
+                parts.append(gen_kernel3(k, m, probe, flags=flags))
     parts.append("}  // namespace")
     parts.append("")
     if diag:
@@ -1024,6 +1069,12 @@ def main():
     for v, probe in (F3_PROBES.items() if diag else ()):
         parts.append(f"    if (k == 64 && m == 32 && fdec_variant() == {v} && a.lane_major == 2u && a.vec <= {F3_MAX_VEC}u) {{")
         parts.append(f"        hipLaunchKernelGGL(rs8_fdec3_k64_m32_probe_{probe}, dim3((a.nblocks + 3) / 4), dim3(256), 0, s, a);")
+        parts.append("        return hipGetLastError() == hipSuccess ? NFEC_OK : NFEC_EDEVICE;")
+        parts.append("    }")
+    for v, (flags, probe) in (F3_VARIANTS.items() if diag else ()):
+        name = f3_name(64, 32, flags, probe)
+        parts.append(f"    if (k == 64 && m == 32 && fdec_variant() == {v} && a.lane_major == 2u && a.vec <= {F3_MAX_VEC}u) {{")
+        parts.append(f"        hipLaunchKernelGGL({name}, dim3((a.nblocks + 3) / 4), dim3(256), 0, s, a);")
         parts.append("        return hipGetLastError() == hipSuccess ? NFEC_OK : NFEC_EDEVICE;")
         parts.append("    }")
     for k, m in shapes:

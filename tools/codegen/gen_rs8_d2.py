@@ -136,8 +136,9 @@ def setup():
     return L
 
 
-def epilogue(r0, w, before_row=None, park=park):
+def epilogue(r0, w, before_row=None, park=park, spol=""):
     """rows [r0, r0 + ROWS) out of the accumulators; w: whose parked offsets (park: where they lie).
+    spol: cache-policy suffix of the parity stores (gen_rs8_t3.py's "nts" variant; after offen).
     before_row(n, r): code ahead of the n-th stored row r (gen_rs8_t3.py merges another wave's
     share there)"""
     L = []
@@ -174,16 +175,16 @@ def epilogue(r0, w, before_row=None, park=park):
         if n == 0:
             assert set(acc) >= {x for q in QUADS for x in q[2:]}
             for q in range(4):
-                L.append(f"buffer_store_dwordx2 v[{acc[2 * q]}:{acc[2 * q + 1]}], v{so[q]}, s[{S_SRS}:{S_SRS + 3}], s{S_ROW} offen")
+                L.append(f"buffer_store_dwordx2 v[{acc[2 * q]}:{acc[2 * q + 1]}], v{so[q]}, s[{S_SRS}:{S_SRS + 3}], s{S_ROW} offen{spol}")
             continue
         for p in range(2):
             Q = QUADS[p]
             L += [f"v_mov_b32 v{Q[i]}, v{acc[4 * p + i]}" for i in range(4)]
             # (a store of more than 8 bytes needs a wait state before its data registers change)
-            L += [f"buffer_store_dwordx4 v[{Q[0]}:{Q[3]}], v{SO_F[p]}, s[{S_SRS}:{S_SRS + 3}], s{S_ROW} offen", "s_nop 1"]
+            L += [f"buffer_store_dwordx4 v[{Q[0]}:{Q[3]}], v{SO_F[p]}, s[{S_SRS}:{S_SRS + 3}], s{S_ROW} offen{spol}", "s_nop 1"]
         L += [f"s_cmp_lg_u64 s[{S_HALF}:{S_HALF + 1}], 0", f"s_cbranch_scc0 Lnohalf{r}_%="]
         for p in range(2):
-            L.append(f"buffer_store_dwordx2 v[{acc[4 * p]}:{acc[4 * p + 1]}], v{SO_E[p]}, s[{S_SRS}:{S_SRS + 3}], s{S_ROW} offen")
+            L.append(f"buffer_store_dwordx2 v[{acc[4 * p]}:{acc[4 * p + 1]}], v{SO_E[p]}, s[{S_SRS}:{S_SRS + 3}], s{S_ROW} offen{spol}")
         L.append(f"Lnohalf{r}_%=:")
     return L
 

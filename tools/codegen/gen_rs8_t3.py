@@ -70,6 +70,12 @@ assert 2 * 2 * ROUND * SLOT <= EX0
 # timing probes (diagnostic library, NFEC_T3_VARIANT=<id>; wrong parity on purpose): VALU + LDS
 # only (no DMA), memory only (DMA and stores: no arithmetic, no ring reads, no role A)
 PROBES = {1: "noload", 2: "nocompute"}
+# stream variants (diagnostic library, the ids after the probes'): a cache policy on the parity stores
+# ("nts") or on the column DMA ("ntl"), each as the whole kernel and as its memory-only probe.  The
+# assembler takes the DMA's policy only between offen and lds, a spelling the committed codegen
+# tests' interpreter refuses, so "ntl" can be measured but not adopted.
+POLICY = {"nts": {"spol": " nt"}, "ntl": {"lpol": " nt"}}
+VARIANTS = {3: ("nts", None), 4: ("nts", "nocompute"), 5: ("ntl", None), 6: ("ntl", "nocompute")}
 
 
 def ring(w, s):
@@ -184,7 +190,7 @@ def role_a(G, probe=None):
     return L
 
 
-def role_bc(G, w, probe=None):
+def role_bc(G, w, probe=None, lpol="", spol=""):
     """role B (w = 0: rows 0..15, S2) or C (w = 1: rows 16..31, S3): ring w, exchange half w"""
     noload, nocompute = probe == "noload", probe == "nocompute"
     steps, _ = plan(G)
@@ -202,7 +208,7 @@ def role_bc(G, w, probe=None):
                f"s_add_u32 s{S_LRS}, s{S_IB}, s{S_COL}", f"s_addc_u32 s{S_LRS + 1}, s{S_IB + 1}, 0"]
         for p in range(2):
             out += [f"s_add_u32 m0, %[lb], {ring(w, s) + 1024 * p}", "s_nop 0",
-                    f"buffer_load_dwordx4 v{DP[p]}, s[{S_LRS}:{S_LRS + 3}], 0 offen lds"]
+                    f"buffer_load_dwordx4 v{DP[p]}, s[{S_LRS}:{S_LRS + 3}], 0 offen{lpol} lds"]
         return out
 
     def raw_read(s):
@@ -251,7 +257,7 @@ def role_bc(G, w, probe=None):
             pre, ups = times(st["s3x"], O, ALL, first=False)
             L += ["s_waitcnt lgkmcnt(0)"] + pre + ups
     if nocompute:
-        return L + D2.epilogue(ROWS * w, w, park=park)
+        return L + D2.epilogue(ROWS * w, w, park=park, spol=spol)
 
     def merge(n, r):
         """role A's share of row r: hand-over round n // ROUND"""
@@ -260,11 +266,11 @@ def role_bc(G, w, probe=None):
             out.append(f"ds_read_b64 v[{Y[2 * i]}:{Y[2 * i + 1]}], %[la] offset:{hand(n // ROUND % 2, w, n % ROUND) + 512 * i}")
         out.append("s_waitcnt lgkmcnt(0)")
         return out + [f"v_xor_b32 v{a}, v{Y[i]}, v{a}" for i, a in enumerate(accs(r))]
-    return L + D2.epilogue(ROWS * w, w, merge, park)
+    return L + D2.epilogue(ROWS * w, w, merge, park, spol)
 
 
-def role_asm(G, role, probe=None):
-    return role_a(G, probe) if role == 0 else role_bc(G, role - 1, probe)
+def role_asm(G, role, probe=None, policy=None):
+    return role_a(G, probe) if role == 0 else role_bc(G, role - 1, probe, **POLICY.get(policy, {}))
 
 
 def compact_roles(roles, width=200):
@@ -286,10 +292,10 @@ def compact_roles(roles, width=200):
     return defs, [F3.f3_compact_lines(ls, width, FORMS) for ls in roles]
 
 
-def gen_kernel(probe=None, compact=False):
+def gen_kernel(probe=None, compact=False, policy=None):
     G = generator(K, M)
-    name = f"rs8_t3_enc_k{K}_m{M}" + (f"_probe_{probe}" if probe else "")
-    asm = [role_asm(G, r, probe) for r in range(NW)]
+    name = f"rs8_t3_enc_k{K}_m{M}" + (f"_{policy}" if policy else "") + (f"_probe_{probe}" if probe else "")
+    asm = [role_asm(G, r, probe, policy) for r in range(NW)]
     if compact:
         defs, packed = compact_roles(asm)
         bodies = ["\n        ".join(p) for p in packed]
@@ -393,6 +399,10 @@ def main():
         for probe in PROBES.values():
             parts.append(gen_kernel(probe)[1])
             parts.append(launcher(f"{name}_probe_{probe}", f"launch_{name}_probe_{probe}"))
+        vname = {v: f"{name}_{pol}" + (f"_probe_{probe}" if probe else "") for v, (pol, probe) in VARIANTS.items()}
+        for v, (pol, probe) in VARIANTS.items():
+            parts.append(gen_kernel(probe, policy=pol)[1])
+            parts.append(launcher(vname[v], f"launch_{vname[v]}"))
         parts += [
             "}  // namespace",
             "",
@@ -404,6 +414,8 @@ def main():
         ]
         for v, probe in PROBES.items():
             parts.append(f"    if (v == {v}) return launch_{name}_probe_{probe}(a, s);")
+        for v in VARIANTS:
+            parts.append(f"    if (v == {v}) return launch_{vname[v]}(a, s);")
         parts += ["    return NFEC_ENOTSUP;", "}", "", "}  // namespace nfec"]
     open(path, "w").write("\n".join(parts) + "\n")
 

@@ -72,7 +72,9 @@ ENC_CASES = [
     (NFEC_RS16, 40, 10, 65, 72, 3),
     (NFEC_RS16, 400, 100, 64, 64, 2),
     (NFEC_RS16, 100, 20, 1400, 1400, 3),
-    (NFEC_RS16, 700, 200, 64, 64, 2),     # offsets table > 16 MB: the exp-table encode kernel
+    # selector table > 16 MB, so no gf16_bs_encode: a dense batch still runs the tower kernels; the
+    # exp-table encode kernel (gf16_matmul) takes it past their offsets, tests/test_gpu_layouts.py
+    (NFEC_RS16, 700, 200, 64, 64, 2),
     (NFEC_MDP, 64, 32, 1400, 1400, 4),
     (NFEC_MDP, 16, 4, 33, 40, 5),
 ]
@@ -170,7 +172,12 @@ def test_decode_matches_oracle(orc, kind, k, m, vec, nb, es, ep):
 def test_rs16_decode_layout_past_the_t3_offset_bound(orc):
     """RS16 decode stage 1 by the shared-table encode kernel needs every piece offset
     of an 8 KiB item group below 2^31 (t3_prepare).  A padded seg_stride past that bound must
-    decode through the gather stage, not fail after the plan marked blocks for the encode path."""
+    decode through the gather stage, not fail after the plan marked blocks for the encode path.
+    That was the shared-table codec's bound (8192 / 64 + 2 = 130 blocks).  The default codec now
+    runs the tower kernel, whose group spans 4096 / 64 + 2 = 66 blocks: 66 x 50 x 352 KiB is below
+    2^31, so this layout decodes on the tower route (asserted below) and is past no bound of it.
+    Both sides of the tower's bound, and the gather stage behind it, are in
+    tests/test_gpu_layouts.py (dec-rs16-40-10-tower)."""
     k, m, vec, nb, es = 40, 10, 64, 3, 6
     stride = 352 * 1024                       # 130 blocks x (50 x 352 KiB) > 2^31
     enc, dec = _codecs(NFEC_RS16, k, m, vec)
@@ -180,9 +187,12 @@ def test_rs16_decode_layout_past_the_t3_offset_bound(orc):
     ref = host.copy()
     st_ref = orc.decode_blocks(NFEC_RS16, k, m, vec, ref, locs, counts)
     dev = torch.from_numpy(host).cuda()
+    p0 = dec.decode_paths()
     st = dec.decode_blocks(dev, torch.from_numpy(locs.astype(np.int16)).cuda(),
                            torch.from_numpy(counts.astype(np.int16)).cuda())
     torch.cuda.synchronize()
+    p1 = dec.decode_paths()
+    assert {n: p1[n] - p0[n] for n in p1 if p1[n] != p0[n]} == {"rs16_tower": 1}
     assert np.array_equal(st.cpu().numpy(), st_ref) and (st_ref == es).all()
     assert np.array_equal(dev.cpu().numpy(), ref)
 
@@ -208,9 +218,12 @@ def test_decode_shortened_blocks(orc, kind):
 
 @pytest.mark.parametrize("kind", [NFEC_RS8, NFEC_RS16])
 def test_decode_shortened_many_erasures_generic_plan(orc, kind):
-    """RS8 and RS16 through the generic plan with 65..255 erasures per block and per-block
-    numData: the log-domain elimination with its lists in the block's global scratch
-    (min(k, m) > 64), shortened-block column offsets included."""
+    """RS8 and RS16 with 65..255 erasures per block and per-block numData, shortened-block column
+    offsets included.  A dense batch of these codes does not reach the generic plan its name says:
+    RS8 runs the closed-form one-pass repair map (rs8_plan_rt, the "runtime" counter) and RS16 the
+    tower route (rs16_plan_cf, "rs16_tower"), both asserted here.  The generic plan with its lists
+    in the block's global scratch (rs_plan_kernel, min(k, m) > 64) takes these very blocks in
+    tests/test_gpu_layouts.py (dec-rs8-128-127-generic-big-plan), where the layout selects it."""
     k, m, vec, nb = 128, 127, 72, 4
     nd = np.array([128, 100, 90, 127], np.uint16)
     enc, dec = _codecs(kind, k, m, vec)
@@ -222,10 +235,13 @@ def test_decode_shortened_many_erasures_generic_plan(orc, kind):
     st_ref = orc.decode_blocks(kind, k, m, vec, ref, locs, counts, nd)
     assert (st_ref == counts).all()
     dev = torch.from_numpy(host).cuda()
+    p0 = dec.decode_paths()
     st = dec.decode_blocks(dev, torch.from_numpy(locs.astype(np.int16)).cuda(),
                            torch.from_numpy(counts.astype(np.int16)).cuda(),
                            num_data=torch.from_numpy(nd.astype(np.int16)).cuda())
     torch.cuda.synchronize()
+    p1 = dec.decode_paths()
+    assert {n: p1[n] - p0[n] for n in p1 if p1[n] != p0[n]} == {"runtime" if kind == NFEC_RS8 else "rs16_tower": 1}
     assert np.array_equal(st.cpu().numpy(), st_ref)
     assert np.array_equal(dev.cpu().numpy(), ref)
 
@@ -548,11 +564,13 @@ def test_fused_decode_random_loss(orc, m, ne):
 
 @pytest.mark.parametrize("m,codeword", [(32, True), (32, False), (16, True), (16, False)])
 def test_mdp_snippet_solve(orc, m, codeword):
-    """MDP decode through the bit-sliced snippet solve (gen_solve_asm.hip, blocks with <= 16
-    erased source vectors and <= 96 survivors) and, for the rest of the batch, the generic
-    kernel.  Erasures over source and parity, shortened blocks, and (codeword=False) survivors
-    that are not a codeword: the reference's syndrome / Forney chain is a fixed linear map of
-    all survivors, so the bytes must match it for any input."""
+    """MDP decode of blocks with 1..20 erasures over source and parity, shortened blocks, and
+    (codeword=False) survivors that are not a codeword: the reference's syndrome / Forney chain is
+    a fixed linear map of all survivors, so the bytes must match it for any input.  Despite its
+    name a dense batch runs the runtime-coefficient repair (MDP_RT: mdp_plan, rs8_rt; asserted
+    below), not the snippet solve: mdp_solve_bs (gen_solve_asm.hip, blocks with <= 16 erased source
+    vectors and <= 96 survivors) and the generic kernel behind it take a batch only past rs8_rt's
+    offsets, tests/test_gpu_layouts.py (dec-mdp-64-32-v1400-solve-bs)."""
     k, vec, nb = 64, 1400, 40
     _, dec = _codecs(NFEC_MDP, k, m, vec)
     nd = np.full(nb, k, np.uint16)
@@ -569,17 +587,20 @@ def test_mdp_snippet_solve(orc, m, codeword):
     counts = np.zeros(nb, np.uint16)
     for b in range(nb):
         n = int(nd[b]) + m
-        ne = min(m, 1 + b % 20)  # 1..20 erasures: e > 16 source ones go to the generic kernel
+        ne = min(m, 1 + b % 20)  # 1..20 erasures, on both sides of the snippet solve's 16 source ones
         locs[b, :ne] = np.sort(rng.choice(n, ne, replace=False))
         counts[b] = ne
     _erase(blocks, locs, counts)
     ref = blocks.copy()
     st_ref = orc.decode_blocks(NFEC_MDP, k, m, vec, ref, locs, counts, nd)
     dev = torch.from_numpy(blocks).cuda()
+    p0 = dec.decode_paths()
     st = dec.decode_blocks(dev, torch.from_numpy(locs.astype(np.int16)).cuda(),
                            torch.from_numpy(counts.astype(np.int16)).cuda(),
                            num_data=torch.from_numpy(nd.astype(np.int16)).cuda())
     torch.cuda.synchronize()
+    p1 = dec.decode_paths()
+    assert {n: p1[n] - p0[n] for n in p1 if p1[n] != p0[n]} == {"runtime": 1}
     assert np.array_equal(st.cpu().numpy(), st_ref)
     assert np.array_equal(dev.cpu().numpy(), ref)
 

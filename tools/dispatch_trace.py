@@ -18,6 +18,11 @@ of 4 blocks: three chunks, one per slot, the last ragged; the 13-block case reus
 Trace them with `--kernel-trace --memory-copy-trace --output-format csv json`: `join` then also
 gives the multiset of copies, [direction, bytes, how many] (the JSON output carries the sizes).
 
+The *_by_layout cases reach the rungs that only a batch's layout selects on the product library
+(the knobs that used to force them are compiled out of it): the batch is embedded in a pool at the
+first block_stride the rung before refuses, with tests/batch_layouts.py, which names the bound of
+each (`layout`: the id of one of its LADDERS; its block count replaces the 9).
+
 The rx_ingest case runs encode, nfec_tx_list and nfec_tx_emit into a wire buffer and then the
 receiver intake, nfec_rx_ingest, on that buffer.
 """
@@ -28,9 +33,11 @@ import os
 import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))  # batch_layouts
 
 NB = 9
 SHARED = 1  # NFEC_OPT_RS16_SHARED_TABLES
+TMVP_OFF, TMVP_ON = 2, 4  # NFEC_OPT_RS16_TOEPLITZ_OFF / _ON
 
 # name: (call, kind, k, m, vec, keyword options)
 #   erase: "src16" 16 random source slots per block, "src+par" the same plus parity rows 0-15,
@@ -65,6 +72,24 @@ CASES = {
     "enc_rs16_512_128_split": ("enc", "RS16", 512, 128, 64, {}),
     "enc_rs16_32_8_shortened_tower": ("enc", "RS16", 32, 8, 64, {"short": True}),
     "enc_rs16_32_8_shared": ("enc", "RS16", 32, 8, 64, {"opts": SHARED}),
+    # layout: the batch at the first block_stride past the named bound (tests/batch_layouts.py, LADDERS)
+    "dec_rs8_64_32_rt_by_layout": ("dec", "RS8", 64, 32, 1400, {"layout": "dec-rs8-64-32-fixed"}),
+    "dec_rs8_64_32_generic_by_layout": ("dec", "RS8", 64, 32, 1400, {"layout": "dec-rs8-64-32-generic-e16"}),
+    "dec_rs8_128_127_big_plan_by_layout": ("dec", "RS8", 128, 127, 72,
+                                           {"layout": "dec-rs8-128-127-generic-big-plan-a", "erase": 100, "short": True}),
+    "dec_mdp_64_32_solve_by_layout": ("dec", "MDP", 64, 32, 1400, {"layout": "dec-mdp-64-32-v1400-solve-bs"}),
+    "dec_mdp_64_32_v1397_generic_by_layout": ("dec", "MDP", 64, 32, 1397, {"layout": "dec-mdp-64-32", "erase": 20}),
+    "dec_rs16_40_10_generic_by_layout": ("dec", "RS16", 40, 10, 64, {"layout": "dec-rs16-40-10-tower", "erase": 8}),
+    "dec_rs16_40_10_shared_gather_by_layout": ("dec", "RS16", 40, 10, 64,
+                                               {"layout": "dec-rs16-40-10-shared-stage1", "erase": 8, "opts": SHARED}),
+    "enc_rs8_64_32_v24_q4_by_layout": ("enc", "RS8", 64, 32, 24, {"layout": "enc-rs8-64-32-t3"}),
+    "enc_rs8_64_16_rt_by_layout": ("enc", "RS8", 64, 16, 1408, {"layout": "enc-rs8-64-16-fixed"}),
+    "enc_rs8_20_10_generic_by_layout": ("enc", "RS8", 20, 10, 8, {"layout": "enc-rs8-20-10-rt"}),
+    "enc_mdp_20_10_generic_by_layout": ("enc", "MDP", 20, 10, 8, {"layout": "enc-mdp-20-10-rt"}),
+    "enc_rs16_40_10_bs_by_layout": ("enc", "RS16", 40, 10, 64, {"layout": "enc-rs16-40-10-bs", "opts": TMVP_OFF}),
+    "enc_rs16_700_200_matmul_by_layout": ("enc", "RS16", 700, 200, 64,
+                                          {"layout": "enc-rs16-700-200-matmul", "opts": TMVP_OFF}),
+    "enc_rs16_32_8_shared_bs_by_layout": ("enc", "RS16", 32, 8, 64, {"layout": "enc-rs16-32-8-shared", "opts": SHARED | TMVP_OFF}),
     # host: "pinned" / "pageable" strided blocks, "vectors" segment lists; stride: seg_stride
     "host_enc_rs8_pinned": ("enc", "RS8", 64, 32, 1400, {"host": "pinned"}),
     "host_enc_rs8_pageable": ("enc", "RS8", 64, 32, 1400, {"host": "pageable"}),
@@ -102,6 +127,24 @@ def _host_call(codec, call, how, blocks, nd, acc, locs=None, counts=None):
     fn(segs, *dec, num_data=hnd, accumulate=acc)
 
 
+def _embedded(ladder_id, k, m, vec):
+    """the case's batch at the first block_stride its ladder's bound refuses: a strided view of a
+    pool that holds just its extent, the slots zeroed (the pool's other bytes are never touched)"""
+    import torch
+
+    import batch_layouts as L
+
+    c = L.LADDER_BY_ID[ladder_id]
+    assert (c.k, c.m, c.vec) == (k, m, vec)
+    lay = L.ladder_layouts(c)[-1][1]
+    lay.check(k, m, vec)
+    pool = torch.empty(lay.extent, dtype=torch.uint8, device="cuda")
+    blocks = L.embed(pool, lay.lead, lay.nb, lay.slots, lay.seg_stride, lay.block_stride)
+    for b in range(lay.nb):
+        blocks[b].zero_()
+    return blocks
+
+
 def run(name):
     import torch
 
@@ -111,7 +154,11 @@ def run(name):
     nb, opts = kw.get("nb", NB), kw.get("opts", 0)
     enc = getattr(C, "NormEncoder" + kind)(options=opts)
     assert enc.Init(k, m, vec)
-    blocks = C.BlockLayout(k, m, vec, kw.get("stride")).empty(nb)
+    if kw.get("layout"):
+        blocks = _embedded(kw["layout"], k, m, vec)
+        nb = blocks.shape[0]
+    else:
+        blocks = C.BlockLayout(k, m, vec, kw.get("stride")).empty(nb)
     how = kw.get("host")
     nd = None
     if kw.get("short"):

@@ -352,8 +352,10 @@ int nfec_rx_erasures_host(uint32_t k, uint32_t m, const uint32_t* received, uint
  * with flush set and nacking_mode NACK_NORMAL (normObject.cpp:1179-1381) and, per block,
  * NormBlock::AppendRepairRequest (normSegment.cpp:524-630).  The caller bounds the call at the last
  * block the sender has finished; the max_pending_block / max_pending_segment form, the NACK's message
- * header, its timers, back-off and suppression stay the caller's, as does what the sender does with
- * a NACK beyond parsing it (hold-off, transmit index, order across receivers).
+ * header, its timers and the back-off draw stay the caller's, as does what the sender does with a
+ * NACK beyond handling it (hold-off, transmit index).  Whether the NACK is sent at all, suppression,
+ * is nfec_rx_handle_repair_content / nfec_rx_repair_pending ("NACK suppression and repair
+ * advertisements on the device").
  *
  * Per block, with nd_b = num_data ? num_data[b] : k and "pending" a clear bit of the reception mask
  * in [0, nd_b + m): e = pending source slots, p = received parity slots.  A block is
@@ -518,7 +520,8 @@ int nfec_tx_emit(const nfec_codec* codec, const nfec_block_batch* batch, const n
  * Every block of the batch counts as held by the sender: it has a NormBlock and its parity exists
  * (the situation after nfec_encode).  Out of scope: the hold-off arm (TxUpdate against the transmit
  * index), several objects per call, SenderRecoverBlock, the stream's LockBlocks / LockSegments,
- * squelch, timers and CC feedback, and NORM_CMD(REPAIR_ADV).
+ * squelch, timers and CC feedback.  The content of NORM_CMD(REPAIR_ADV) is nfec_tx_repair_adv
+ * ("NACK suppression and repair advertisements on the device").
  *
  * The state: caller-allocated arrays, device memory for the device entries, host memory for the
  * *_host entries.  repair has the pending mask's layout.  TxInit is parity = {auto_parity, 0},
@@ -641,6 +644,128 @@ int nfec_tx_end_blocks(const nfec_codec* codec, const uint16_t* num_data, uint32
                        uint32_t mask_stride, const nfec_tx_repair_state* state, void* stream);
 int nfec_tx_end_blocks_host(uint32_t k, uint32_t m, const uint16_t* num_data, uint32_t nblocks,
                             const uint32_t* pending, uint32_t mask_stride, const nfec_tx_repair_state* state);
+
+/* ---- NACK suppression and repair advertisements on the device ----
+ * What makes the repair cycle a multicast one: during its back-off a receiver listens to the NACKs of
+ * the others and to the sender's NORM_CMD(REPAIR_ADV), and stays silent when what it needs has been
+ * asked for already; the sender advertises what it is about to repair.  In the reference:
+ * NormSenderNode::HandleRepairContent (normNode.cpp:1069-1187), called for overheard NACKs
+ * (:1060-1062) and for REPAIR_ADV (:906-911); NormObject::SetRepairs / SetRepairInfo
+ * (normObject.h:274-279) and NormBlock::SetRepairs (normSegment.h:216-222); the decision at the end
+ * of the back-off, NormSenderNode::OnRepairTimeout (normNode.cpp:2362-2390), NormObject::
+ * IsRepairPending(flush) (normObject.cpp:1137-1177) and NormBlock::IsRepairPending
+ * (normSegment.cpp:174-216); on the sender NormSession::SenderBuildRepairAdv (normSession.cpp:
+ * 4598-4708), NormObject::AppendRepairAdv (normObject.cpp:540-683) and NormBlock::AppendRepairAdv
+ * (normSegment.cpp:405-493).  A receiver's round is
+ *   zero the state -> nfec_rx_handle_repair_content x N -> nfec_rx_repair_pending ->
+ *   nfec_rx_repair_requests when it sends,
+ * the sender's
+ *   nfec_tx_handle_nacks x N -> nfec_tx_repair_adv -> nfec_tx_activate_repairs -> ...
+ * One object per call, flush form only (nfec_rx_repair_requests' and nfec_tx_handle_nacks' limits).
+ * Out of scope: timers and the back-off draw, the non-flush form bounded by current_block_id, the
+ * NORM_REPAIR_ADV_FLAG_LIMIT flag of a full advertisement, and CC feedback.
+ *
+ * The receiver's suppression state: caller-allocated arrays, device memory for the device entries,
+ * host memory for the *_host entries; the mask layouts are the reception mask's.  The caller zeroes
+ * all three at the start of a NACK cycle: that is the whole of the reset NormObject::
+ * ReceiverRepairCheck makes when it starts the repair timer (normObject.cpp:1098-1110), so no entry
+ * exists for it. */
+#define NFEC_RX_REPAIR_OBJECT 1u   /* rx_repair_mask names the object */
+#define NFEC_RX_REPAIR_INFO   2u   /* NormObject::repair_info          */
+typedef struct nfec_rx_repair_state {
+    uint32_t* repair;        /* [nblocks][mask_stride]: the receiver's NormBlock::repair_mask */
+    uint32_t* block_repair;  /* [(nblocks + 31) / 32]: NormObject::repair_mask               */
+    uint32_t* object;        /* [1]: NFEC_RX_REPAIR_OBJECT | NFEC_RX_REPAIR_INFO              */
+} nfec_rx_repair_state;
+
+/* HandleRepairContent for one object.  Message i of messages is the repair-request content of one
+ * overheard NORM_NACK or of one NORM_CMD(REPAIR_ADV), at any byte alignment; count_dev is honoured.
+ * Unreadable messages, the loads (aligned chunks of at most 16 bytes that hold a byte of the
+ * message), the parser, where a message is cut short, a request's level, the own / foreign test of
+ * a unit and the block of the batch of an item are nfec_tx_handle_nacks'.  Per unit of this object:
+ *   - INFO level sets NFEC_RX_REPAIR_INFO.
+ *   - OBJECT level sets NFEC_RX_REPAIR_OBJECT; the request's INFO flag is not looked at (:1141-1146).
+ *   - BLOCK level sets NFEC_RX_REPAIR_INFO when the request carries INFO, and the block_repair bits
+ *     of [b0, min(b1, nblocks - 1)]; nothing when b0 > b1 or b0 >= nblocks.
+ *   - SEGMENT level, block b of the first item, sets NFEC_RX_REPAIR_INFO when the request carries
+ *     INFO, applied or not (SetRepairInfo stands in front of FindBlock, :1172).  The unit is applied
+ *     when b < nblocks, nd_b lies in [1, k], last.symbol >= first.symbol and block b is held: it is a
+ *     needing block (class 1) by nfec_rx_repair_requests' classification of `received` at the time
+ *     of the call.  (The reference has a NormBlock for exactly these: an absent block has none, a
+ *     complete or decodable one was decoded and released.)  An applied unit sets the repair bits
+ *     [first.symbol, last.symbol], clipped at nd_b + m.
+ * Every update is an OR: the result depends neither on the order of the messages, nor on how they
+ * are split over calls, nor on the order in which the device's atomics land (the reference's
+ * freshObject / freshBlock are lookup caches).  There is no workspace and no capacity.  totals
+ * (device uint64 [6]) = {units in all, SEGMENT units applied, SEGMENT units not applied plus units
+ * ignored (foreign, or of a request without a level), block_repair bits newly set, messages cut
+ * short, messages unreadable}; the newly-set count is exact however many messages name a block.
+ * `received` is only read.  Asynchronous on stream, on the codec device that holds state->repair;
+ * owns no codec state.  NFEC_EINVAL for a fec_id / fec_m pair nfec_payload_id_read refuses and for
+ * fec_id 0, for null arrays and a mask_stride below (k + m + 31) / 32.  count == 0 or nblocks == 0
+ * is NFEC_OK with zero totals. */
+int nfec_rx_handle_repair_content(const nfec_codec* codec, const nfec_rx_messages* messages, uint8_t fec_id,
+                                  uint8_t fec_m, uint16_t object_id, uint32_t first_block_id,
+                                  const uint32_t* received, uint32_t mask_stride, const uint16_t* num_data,
+                                  uint32_t nblocks, const nfec_rx_repair_state* state,
+                                  uint64_t* totals /* device [6] */, void* stream);
+/* nfec_rx_handle_repair_content's rule on host arrays: no codec, no GPU.  Also NFEC_EINVAL for k or
+ * m of 0 and k + m > 65536. */
+int nfec_rx_handle_repair_content_host(uint32_t k, uint32_t m, const nfec_rx_messages* messages, uint8_t fec_id,
+                                       uint8_t fec_m, uint16_t object_id, uint32_t first_block_id,
+                                       const uint32_t* received, uint32_t mask_stride, const uint16_t* num_data,
+                                       uint32_t nblocks, const nfec_rx_repair_state* state, uint64_t* totals);
+
+/* The decision at the end of the back-off, flush form: does the receiver send a NACK for the object?
+ * Per block, with the class and the requested slots of nfec_rx_repair_requests: a silent block is
+ * not pending; an absent block is pending unless its block_repair bit is set; a needing block is
+ * pending unless its block_repair bit is set or every requested slot has its repair bit set
+ * (NormBlock::IsRepairPending: the slots it presets are exactly the pending slots the request does
+ * not name).  The object is suppressed when NFEC_RX_REPAIR_OBJECT is set; otherwise it sends when
+ * flags holds NFEC_NACK_INFO (the object's NORM_INFO is pending) and NFEC_RX_REPAIR_INFO is clear,
+ * or when any block is pending.  The state is only read: the reference destroys its masks here
+ * (XCopy), this call does not.  pending_blocks: device uint32 [(nblocks + 31) / 32], may be NULL:
+ * bit b % 32 of word b / 32 is set when block b is pending; every word is written, bits at or past
+ * nblocks are zero, the caller need not zero it.  totals (device uint64 [4]) = {send: 0 or 1,
+ * blocks pending, needing blocks suppressed, absent blocks suppressed}; the three block counts are
+ * the full numbers whatever the object word says.  Asynchronous on stream, on the codec device that
+ * holds the mask.  NFEC_EINVAL for flags other than NFEC_NACK_INFO, null arrays and a mask_stride
+ * below (k + m + 31) / 32.  nblocks == 0 is NFEC_OK with zero totals and reads no state. */
+int nfec_rx_repair_pending(const nfec_codec* codec, const uint32_t* received, uint32_t mask_stride,
+                           const uint16_t* num_data, uint32_t nblocks, const nfec_rx_repair_state* state,
+                           uint32_t flags, uint32_t* pending_blocks, uint64_t* totals /* device [4] */,
+                           void* stream);
+int nfec_rx_repair_pending_host(uint32_t k, uint32_t m, const uint32_t* received, uint32_t mask_stride,
+                                const uint16_t* num_data, uint32_t nblocks, const nfec_rx_repair_state* state,
+                                uint32_t flags, uint32_t* pending_blocks, uint64_t* totals);
+
+/* The repair-request content of a NORM_CMD(REPAIR_ADV) from the sender's repair state as it stands
+ * after nfec_tx_handle_nacks and before nfec_tx_activate_repairs.  The arguments and outputs are
+ * nfec_rx_repair_requests' with the state in place of the reception mask (mask_stride is
+ * state->repair's; only repair, block_repair and object are read) and without flags: INFO is
+ * NFEC_TX_REPAIR_INFO, read from the object word on the device.  Per block: nd_b outside [1, k] is
+ * silent; a set block_repair bit makes a whole block (class 2, what an absent block is to a NACK);
+ * else any repair bit in [0, nd_b + m) makes class 1 with those bits as the requested slots; else
+ * silent.  From there the runs, units, chains and requests are those of "repair requests on the
+ * device", word for word: NormObject::AppendRepairAdv is the walk of AppendRepairRequest over
+ * another mask, and one set of kernels runs both.  totals = {bytes, requests, blocks with segment
+ * requests, whole blocks}; block_start's second column holds the classes.
+ * With NFEC_TX_REPAIR_OBJECT set the content is one request and nothing of the blocks
+ * (normSession.cpp:4681): form ITEMS, flags OBJECT (INFO is not added: SenderBuildRepairAdv's
+ * request never carries it), one item {object id, block 0, block length k, symbol 0}; every row of
+ * block_start is {0, 0} and totals = {bytes, 1, 0, 0}.  A quirk of the reference that is not
+ * reproduced: its loop emits this request only when another object follows in the table (:4622
+ * tests NULL != nextObject), so the last object's is lost; a caller that wants that drops the
+ * content.  NFEC_EINVAL as nfec_rx_repair_requests, and for null state arrays; nblocks == 0 is
+ * NFEC_OK with zero totals and reads no state. */
+int nfec_tx_repair_adv(const nfec_codec* codec, const nfec_tx_repair_state* state, uint32_t mask_stride,
+                       const uint16_t* num_data, uint32_t nblocks, uint8_t fec_id, uint8_t fec_m,
+                       uint16_t object_id, uint32_t first_block_id, uint32_t max_units, void* content,
+                       uint64_t capacity, uint64_t* block_start, uint64_t* totals, void* stream);
+int nfec_tx_repair_adv_host(uint32_t k, uint32_t m, const nfec_tx_repair_state* state, uint32_t mask_stride,
+                            const uint16_t* num_data, uint32_t nblocks, uint8_t fec_id, uint8_t fec_m,
+                            uint16_t object_id, uint32_t first_block_id, uint32_t max_units, void* content,
+                            uint64_t capacity, uint64_t* block_start, uint64_t* totals);
 
 /* ---- object segmentation on the device ----
  * The mapping between a NORM data object (a contiguous run of bytes) and the source slots of its

@@ -14,7 +14,8 @@ from .codec import (  # noqa: F401
     received_mask, erasures_from_received_host, rx_parse_host, tx_list_host, rx_repair_requests_host,
     repair_parse_host, repair_max_units, repair_content_bound, object_layout, object_segment, object_block_sizes,
     StreamState, stream_frame_host, TxRepairState, tx_repair_state, tx_handle_nacks_host, tx_activate_repairs_host,
-    tx_end_blocks_host,
+    tx_end_blocks_host, RxRepairState, rx_repair_state, rx_handle_repair_content_host, rx_repair_pending_host,
+    tx_repair_adv_host,
 )
 
 __version__ = "0.1.0"

@@ -27,6 +27,8 @@ REPAIR_ITEMS, REPAIR_RANGES = 1, 2
 REPAIR_SEGMENT, REPAIR_BLOCK, REPAIR_INFO, REPAIR_OBJECT = 1, 2, 4, 8
 # nfec_tx_repair_state: the object word
 NFEC_TX_REPAIR_OBJECT, NFEC_TX_REPAIR_INFO, NFEC_TX_PENDING_INFO = 1, 2, 4
+# nfec_rx_repair_state: the object word
+NFEC_RX_REPAIR_OBJECT, NFEC_RX_REPAIR_INFO = 1, 2
 NFEC_FEATURE_RS16_TOEPLITZ, NFEC_FEATURE_RS16_TOEPLITZ2 = 1, 2
 NFEC_OPT_RS16_SHARED_TABLES, NFEC_OPT_RS16_TOEPLITZ_OFF, NFEC_OPT_RS16_TOEPLITZ_ON, NFEC_OPT_HOST_ONLY = 1, 2, 4, 8
 NFEC_OPT_RS16_TOEPLITZ_ONE_LEVEL = 16
@@ -86,6 +88,15 @@ class TxRepairStateStruct(ctypes.Structure):
     _fields_ = [
         ("repair", ctypes.c_void_p),
         ("parity", ctypes.c_void_p),
+        ("block_repair", ctypes.c_void_p),
+        ("object", ctypes.c_void_p),
+    ]
+
+
+class RxRepairStateStruct(ctypes.Structure):
+    """nfec_rx_repair_state: a receiver's suppression state (device arrays, or host arrays for the *_host entries)."""
+    _fields_ = [
+        ("repair", ctypes.c_void_p),
         ("block_repair", ctypes.c_void_p),
         ("object", ctypes.c_void_p),
     ]
@@ -261,6 +272,16 @@ _SIGS = {
     "nfec_tx_activate_repairs_host": (_I, [_U32, _U32, _P, _U32, _U32, _P, _U32, ctypes.POINTER(TxRepairStateStruct), _P]),
     "nfec_tx_end_blocks": (_I, [_P, _P, _U32, _P, _U32, ctypes.POINTER(TxRepairStateStruct), _P]),
     "nfec_tx_end_blocks_host": (_I, [_U32, _U32, _P, _U32, _P, _U32, ctypes.POINTER(TxRepairStateStruct)]),
+    "nfec_rx_handle_repair_content": (_I, [_P, ctypes.POINTER(RxMessages), _U8, _U8, _U16, _U32, _P, _U32, _P, _U32,
+                                           ctypes.POINTER(RxRepairStateStruct), _P, _P]),
+    "nfec_rx_handle_repair_content_host": (_I, [_U32, _U32, ctypes.POINTER(RxMessages), _U8, _U8, _U16, _U32, _P, _U32, _P,
+                                                _U32, ctypes.POINTER(RxRepairStateStruct), _P]),
+    "nfec_rx_repair_pending": (_I, [_P, _P, _U32, _P, _U32, ctypes.POINTER(RxRepairStateStruct), _U32, _P, _P, _P]),
+    "nfec_rx_repair_pending_host": (_I, [_U32, _U32, _P, _U32, _P, _U32, ctypes.POINTER(RxRepairStateStruct), _U32, _P, _P]),
+    "nfec_tx_repair_adv": (_I, [_P, ctypes.POINTER(TxRepairStateStruct), _U32, _P, _U32, _U8, _U8, _U16, _U32, _U32, _P,
+                                _U64, _P, _P, _P]),
+    "nfec_tx_repair_adv_host": (_I, [_U32, _U32, ctypes.POINTER(TxRepairStateStruct), _U32, _P, _U32, _U8, _U8, _U16, _U32,
+                                     _U32, _P, _U64, _P, _P]),
     "nfec_object_layout_for": (_I, [_U64, _U32, _U32, ctypes.POINTER(ObjectLayout)]),
     "nfec_object_segment": (_I, [ctypes.POINTER(ObjectLayout), _U32, _U32, ctypes.POINTER(_U64), ctypes.POINTER(_U32)]),
     "nfec_object_block_sizes": (_I, [ctypes.POINTER(ObjectLayout), _U32, _U32, _P]),

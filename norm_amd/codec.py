@@ -475,6 +475,103 @@ class _Codec:
                                            _tensor_ptr(pending, "pending"), state.mask_stride, ctypes.byref(st),
                                            _stream_handle(stream)), "nfec_tx_end_blocks")
 
+    # -- NACK suppression and repair advertisements (nfec.h, "NACK suppression and repair advertisements on the device") --
+    def rx_repair_state(self, nblocks, k=None, m=None, device=None):
+        """A zeroed suppression state (RxRepairState) for nblocks blocks of k + m slots (default: this
+        codec's) on `device` (default: the codec's first)."""
+        self._need()
+        return rx_repair_state(nblocks, self.ndata if k is None else k, self.npar if m is None else m,
+                               device=f"cuda:{self.device}" if device is None else device)
+
+    def handle_repair_content(self, state, received, payloads, offsets, length, num_data=None, fec_id=5, fec_m=8,
+                              object_id=0, first_block_id=0, count_dev=None, totals=None, stream=None):
+        """Overheard repair-request content into a receiver's suppression state
+        (nfec_rx_handle_repair_content: HandleRepairContent for one object).  state:
+        rx_repair_state(...); received: the receiver's reception mask, only read; message i is
+        payloads[offsets[i] : offsets[i] + length[i]], the content of one NORM_NACK or REPAIR_ADV
+        (offsets int64, length int16).  Returns totals int64 [6] = (units, SEGMENT units applied,
+        units not applied or ignored, block_repair bits newly set, messages cut short, messages
+        unreadable)."""
+        import torch
+
+        self._need()
+        _mask_check(received, state.nblocks)
+        if received.shape[1] != state.mask_stride:
+            raise ValueError("received and state.repair must have one mask_stride")
+        count = offsets.numel()
+        for t, size, what in ((offsets, 8, "offsets"), (length, 2, "length")):
+            if t.element_size() != size or t.numel() != count:
+                raise ValueError(f"{what} must hold {count} elements of {size} bytes")
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous CUDA (HIP) tensor")
+        if count_dev is not None and (count_dev.element_size() != 8 or count_dev.numel() < 1 or not count_dev.is_cuda):
+            raise ValueError("count_dev must be a 64-bit CUDA (HIP) tensor")
+        if payloads.element_size() != 1 or not payloads.is_cuda or not payloads.is_contiguous():
+            raise ValueError("payloads must be a contiguous uint8 CUDA (HIP) tensor")
+        if totals is None:
+            totals = torch.zeros(6, dtype=torch.int64, device=payloads.device)
+        msg = N.RxMessages()
+        msg.payloads = payloads.data_ptr() if payloads.numel() else None
+        msg.payload_bytes = payloads.numel()
+        msg.offsets, msg.length = offsets.data_ptr(), length.data_ptr()
+        msg.count = count
+        msg.count_dev = count_dev.data_ptr() if count_dev is not None else None
+        st = state.struct()
+        N.check(N.lib().nfec_rx_handle_repair_content(self._h, ctypes.byref(msg), fec_id, fec_m, object_id & 0xFFFF,
+                                                      first_block_id & 0xFFFFFFFF, _tensor_ptr(received, "received"),
+                                                      state.mask_stride, _tensor_ptr(num_data, "num_data"), state.nblocks,
+                                                      ctypes.byref(st), _tensor_ptr(totals, "totals"),
+                                                      _stream_handle(stream)), "nfec_rx_handle_repair_content")
+        return totals
+
+    def repair_pending(self, state, received, num_data=None, flags=0, pending_blocks=None, totals=None, stream=None):
+        """The decision at the end of the back-off (nfec_rx_repair_pending).  Returns (totals int64 [4]
+        = (send, blocks pending, needing blocks suppressed, absent blocks suppressed), pending_blocks
+        int32 [(nblocks + 31) // 32]: bit b % 32 of word b // 32 is block b).  The state is only read."""
+        import torch
+
+        self._need()
+        _mask_check(received, state.nblocks)
+        if received.shape[1] != state.mask_stride:
+            raise ValueError("received and state.repair must have one mask_stride")
+        if pending_blocks is None:
+            pending_blocks = torch.empty(max(1, (state.nblocks + 31) // 32), dtype=torch.int32, device=received.device)
+        if totals is None:
+            totals = torch.zeros(4, dtype=torch.int64, device=received.device)
+        st = state.struct()
+        N.check(N.lib().nfec_rx_repair_pending(self._h, _tensor_ptr(received, "received"), state.mask_stride,
+                                               _tensor_ptr(num_data, "num_data"), state.nblocks, ctypes.byref(st), flags,
+                                               _tensor_ptr(pending_blocks, "pending_blocks"), _tensor_ptr(totals, "totals"),
+                                               _stream_handle(stream)), "nfec_rx_repair_pending")
+        return totals, pending_blocks
+
+    def repair_adv(self, state, num_data=None, fec_id=5, fec_m=8, object_id=0, first_block_id=0, max_units=None,
+                   capacity=None, content=None, stream=None):
+        """The repair-request content of a NORM_CMD(REPAIR_ADV) from the sender's repair state
+        (nfec_tx_repair_adv), behind handle_nacks and before activate_repairs: (content uint8
+        [capacity], block_start int64 [nblocks + 1, 2], totals int64 [4]) as repair_requests, with
+        totals = (bytes, requests, blocks with segment requests, whole blocks).  The state is only
+        read."""
+        import torch
+
+        self._need()
+        nb = state.nblocks
+        dev = state.repair.device
+        max_units = repair_max_units(fec_id) if max_units is None else max_units
+        if content is None:
+            capacity = repair_content_bound(self.ndata, self.npar, nb, fec_id) if capacity is None else capacity
+            content = torch.zeros(capacity, dtype=torch.uint8, device=dev)
+        capacity = content.numel() if capacity is None else capacity
+        block_start = torch.zeros((nb + 1, 2), dtype=torch.int64, device=dev)
+        totals = torch.zeros(4, dtype=torch.int64, device=dev)
+        st = state.struct()
+        N.check(N.lib().nfec_tx_repair_adv(self._h, ctypes.byref(st), state.mask_stride, _tensor_ptr(num_data, "num_data"),
+                                           nb, fec_id, fec_m, object_id & 0xFFFF, first_block_id & 0xFFFFFFFF, max_units,
+                                           _tensor_ptr(content, "content"), capacity,
+                                           _tensor_ptr(block_start, "block_start"), _tensor_ptr(totals, "totals"),
+                                           _stream_handle(stream)), "nfec_tx_repair_adv")
+        return content, block_start, totals
+
     # -- object segmentation on the device (nfec.h, "object segmentation on the device") --
     def _object_call(self, obj, layout, blocks):
         self._need()
@@ -1137,6 +1234,167 @@ def tx_end_blocks_host(k, m, state, pending, num_data=None):
     N.check(N.lib().nfec_tx_end_blocks_host(k, m, None if nd is None else nd.ctypes.data, state.nblocks,
                                             pending.ctypes.data, state.mask_stride, ctypes.byref(st)),
             "nfec_tx_end_blocks_host")
+
+
+class RxRepairState:
+    """nfec_rx_repair_state: a receiver's suppression state of one object's batch.  repair 32-bit
+    [nblocks, mask_stride], block_repair 32-bit [max(1, (nblocks + 31) // 32)], object 32-bit [1]:
+    torch tensors on a device, or NumPy arrays for the *_host functions.  Zeroed at the start of a
+    NACK cycle (zero())."""
+
+    FIELDS = ("repair", "block_repair", "object")
+
+    def __init__(self, repair, block_repair, object):
+        self.repair, self.block_repair, self.object = repair, block_repair, object
+
+    @property
+    def nblocks(self):
+        return self.repair.shape[0]
+
+    @property
+    def mask_stride(self):
+        return self.repair.shape[1]
+
+    @property
+    def on_host(self):
+        return not hasattr(self.repair, "is_cuda")
+
+    def arrays(self):
+        return tuple(getattr(self, f) for f in self.FIELDS)
+
+    def struct(self):
+        st = N.RxRepairStateStruct()
+        for f in self.FIELDS:
+            t = getattr(self, f)
+            if self.on_host:
+                if not t.flags["C_CONTIGUOUS"]:
+                    raise ValueError(f"state.{f} must be contiguous")
+                setattr(st, f, t.ctypes.data)
+            else:
+                if not t.is_cuda or not t.is_contiguous():
+                    raise ValueError(f"state.{f} must be a contiguous CUDA (HIP) tensor")
+                setattr(st, f, t.data_ptr())
+        return st
+
+    def zero(self):
+        """The reset at the start of a NACK cycle (in stream order on a device)."""
+        for t in self.arrays():
+            if self.on_host:
+                t[...] = 0
+            else:
+                t.zero_()
+
+    def clone(self):
+        return RxRepairState(*(t.copy() if self.on_host else t.clone() for t in self.arrays()))
+
+    def to_host(self):
+        """The state as NumPy uint32 arrays, a copy."""
+        import numpy as np
+
+        if self.on_host:
+            return self.clone()
+        return RxRepairState(*(t.cpu().numpy().view(np.uint32) for t in self.arrays()))
+
+    def to_device(self, device="cuda"):
+        import numpy as np
+        import torch
+
+        src = self.to_host()
+        return RxRepairState(*(torch.from_numpy(t.view(np.int32).copy()).to(device) for t in src.arrays()))
+
+
+def rx_repair_state(nblocks, k, m, device=None, mask_stride=None):
+    """A zeroed suppression state for nblocks blocks of k + m slots: torch tensors on `device`, or
+    NumPy arrays with device=None."""
+    import numpy as np
+
+    stride = (k + m + 31) // 32 if mask_stride is None else mask_stride
+    state = RxRepairState(np.zeros((nblocks, stride), np.uint32), np.zeros(max(1, (nblocks + 31) // 32), np.uint32),
+                          np.zeros(1, np.uint32))
+    return state if device is None else state.to_device(device)
+
+
+def _host_rx_state(state, received):
+    import numpy as np
+
+    if not state.on_host:
+        raise ValueError("state must hold NumPy arrays (rx_repair_state(..., device=None))")
+    for f in state.FIELDS:
+        if getattr(state, f).dtype != np.uint32:
+            raise ValueError(f"state.{f} must be uint32")
+    mask = np.ascontiguousarray(received).view(np.uint32)
+    if mask.ndim != 2 or mask.shape != state.repair.shape:
+        raise ValueError("received must be a 32-bit array of state.repair's shape")
+    return state.struct(), mask
+
+
+def rx_handle_repair_content_host(k, m, state, received, payloads, offsets, length, num_data=None, fec_id=5, fec_m=8,
+                                  object_id=0, first_block_id=0, count=None, payload_bytes=None):
+    """nfec_rx_handle_repair_content_host: Codec.handle_repair_content on host arrays (no GPU), in
+    place on `state`.  received: NumPy 32-bit array [nblocks, mask_stride], only read; payloads: NumPy
+    uint8 array; offsets / length: one entry per message; count: what count_dev would hold, or None;
+    payload_bytes: the wire buffer's size when it is not payloads.size.  Returns totals uint64 [6]."""
+    import numpy as np
+
+    wire = np.ascontiguousarray(payloads).view(np.uint8).reshape(-1)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    ln = np.ascontiguousarray(length, dtype=np.uint16)
+    if off.size != ln.size:
+        raise ValueError("offsets and length must hold one entry per message")
+    nd = None if num_data is None else np.ascontiguousarray(num_data, dtype=np.uint16)
+    st, mask = _host_rx_state(state, received)
+    count_dev = None if count is None else np.array([count], np.uint64)
+    msg = N.RxMessages()
+    msg.payloads = wire.ctypes.data if wire.size else None
+    msg.payload_bytes = wire.size if payload_bytes is None else payload_bytes
+    msg.offsets, msg.length = off.ctypes.data, ln.ctypes.data
+    msg.count = off.size
+    msg.count_dev = None if count_dev is None else count_dev.ctypes.data
+    totals = np.zeros(6, np.uint64)
+    N.check(N.lib().nfec_rx_handle_repair_content_host(k, m, ctypes.byref(msg), fec_id, fec_m, object_id & 0xFFFF,
+                                                       first_block_id & 0xFFFFFFFF, mask.ctypes.data, state.mask_stride,
+                                                       None if nd is None else nd.ctypes.data, state.nblocks,
+                                                       ctypes.byref(st), totals.ctypes.data),
+            "nfec_rx_handle_repair_content_host")
+    return totals
+
+
+def rx_repair_pending_host(k, m, state, received, num_data=None, flags=0):
+    """nfec_rx_repair_pending_host: Codec.repair_pending on host arrays (no GPU).  Returns (totals
+    uint64 [4], pending_blocks uint32 [(nblocks + 31) // 32])."""
+    import numpy as np
+
+    st, mask = _host_rx_state(state, received)
+    nd = None if num_data is None else np.ascontiguousarray(num_data, dtype=np.uint16)
+    pending_blocks = np.full(max(1, (state.nblocks + 31) // 32), 0xFFFFFFFF if state.nblocks else 0, np.uint32)
+    totals = np.zeros(4, np.uint64)
+    N.check(N.lib().nfec_rx_repair_pending_host(k, m, mask.ctypes.data, state.mask_stride,
+                                                None if nd is None else nd.ctypes.data, state.nblocks, ctypes.byref(st),
+                                                flags, pending_blocks.ctypes.data, totals.ctypes.data),
+            "nfec_rx_repair_pending_host")
+    return totals, pending_blocks
+
+
+def tx_repair_adv_host(k, m, state, num_data=None, fec_id=5, fec_m=8, object_id=0, first_block_id=0, max_units=None,
+                       capacity=None):
+    """nfec_tx_repair_adv_host: Codec.repair_adv on host arrays (no GPU).  state: a TxRepairState of
+    NumPy arrays, only read.  Returns (content uint8 [capacity], block_start uint64 [nblocks + 1, 2],
+    totals uint64 [4])."""
+    import numpy as np
+
+    st = _host_state(state)
+    nb = state.nblocks
+    max_units = repair_max_units(fec_id) if max_units is None else max_units
+    capacity = repair_content_bound(k, m, nb, fec_id) if capacity is None else capacity
+    nd = None if num_data is None else np.ascontiguousarray(num_data, dtype=np.uint16)
+    content = np.zeros(capacity, np.uint8)
+    block_start = np.zeros((nb + 1, 2), np.uint64)
+    totals = np.zeros(4, np.uint64)
+    N.check(N.lib().nfec_tx_repair_adv_host(k, m, ctypes.byref(st), state.mask_stride,
+                                            None if nd is None else nd.ctypes.data, nb, fec_id, fec_m, object_id & 0xFFFF,
+                                            first_block_id & 0xFFFFFFFF, max_units, content.ctypes.data, capacity,
+                                            block_start.ctypes.data, totals.ctypes.data), "nfec_tx_repair_adv_host")
+    return content, block_start, totals
 
 
 def tx_list_host(k, m, vector_size, pending, num_data=None, seg_length=None, gap=0, capacity=None):

@@ -13,8 +13,16 @@
 // No unit looks ahead: a request's header is written by whoever closes it -- the unit that opens
 // the next request, the needing block that ends the chain, or the end of the walk -- because the
 // closed request's items are the bytes right in front of the closer.
+//
+// ADV: the same three kernels over the sender's repair state give the repair-request content of a
+// NORM_CMD(REPAIR_ADV) (NormObject::AppendRepairAdv, normObject.cpp:540-683, the same walk): a
+// block's class and request words come from its block_repair bit and its repair mask
+// (suppress_layout.hpp), INFO from the object word, and an object that is repaired as a whole is
+// one OBJECT request written where the walk ends.
 #include "nack_layout.hpp"
 #include "nfec_internal.hpp"
+#include "repair_wave.hpp"
+#include "suppress_layout.hpp"
 #include "wave.hpp"
 
 namespace nfec {
@@ -73,50 +81,6 @@ __device__ __forceinline__ SegVal seg_behind(SegVal inc, SegVal carry)
 
 // ---- one block ----
 
-struct BlockShape {
-    uint32_t cls;
-    NackCut cut;
-};
-
-// e, p, whether anything arrived, and the m-th pending slot: one pass over the block's words, 64 a
-// round, the pending count carried between rounds.  The lane whose word holds the m-th pending slot
-// steps to it through its own 32 bits.
-__device__ __forceinline__ BlockShape block_shape(const NackArgs& a, const uint32_t* __restrict__ mask, uint32_t nd,
-                                                  uint32_t lane)
-{
-    BlockShape r = {NACK_SILENT, {0u, 0u}};
-    if (nd < 1 || nd > a.k) return r;
-    const uint32_t n = nd + a.m, w_end = (n + 31u) >> 5;
-    uint32_t e = 0, p = 0, any = 0, before = 0, mth = 0;
-    for (uint32_t w0 = 0; w0 < w_end; w0 += 64) {
-        const uint32_t w = w0 + lane;
-        const uint32_t word = w < w_end ? mask[w] : 0u;
-        const uint32_t valid = nack_range_bits(w, 0, n), src = nack_range_bits(w, 0, nd);
-        const uint32_t pend = ~word & valid;
-        e += __popc(pend & src);
-        p += __popc(word & valid & ~src);
-        any |= word & valid;
-        const uint32_t cnt = __popc(pend), inc = wave_scan(cnt, lane), exc = before + inc - cnt;
-        const bool hit = exc < a.m && a.m <= exc + cnt;
-        uint32_t slot = 0;
-        if (hit) {
-            uint32_t t = pend;
-            for (uint32_t i = a.m - exc; i > 1; --i) t &= t - 1u;
-            slot = (w << 5) + (__ffs(t) - 1u);
-        }
-        const uint64_t owner = __ballot(hit);
-        if (owner) mth = __shfl(slot, __ffsll((unsigned long long)owner) - 1, 64);
-        before += __shfl(inc, 63, 64);
-    }
-    e = __shfl(wave_scan(e, lane), 63, 64);
-    p = __shfl(wave_scan(p, lane), 63, 64);
-    any = __any(any != 0);
-    r.cls = uniform(nack_class(nd, a.k, e, p, any));
-    r.cut = nack_cut(nd, a.m, e, mth);
-    r.cut.lo = uniform(r.cut.lo), r.cut.hi = uniform(r.cut.hi);
-    return r;
-}
-
 // The chain of a needing block.  Lane L of a round takes the runs that start in its word: from the
 // word, the top bits of the one before and the low bits of the one behind it has the run starts and
 // their three length classes as bit masks.  Three segmented scans over the wave, each seeded by
@@ -126,16 +90,19 @@ __device__ __forceinline__ BlockShape block_shape(const NackArgs& a, const uint3
 // WRITE: the lane writes its runs' items and closes the requests its runs end; a long run's end
 // item is written by the lane whose word holds the end, at the offset of the last unit in front
 // of its own.  Serial work per lane: the run starts of its one word.
-template <bool WRITE>
-__device__ __forceinline__ void block_requests(const NackArgs& a, const uint32_t* __restrict__ mask, uint32_t b,
+// ADV: mask is the block's repair mask, whose set bits are the requested slots.
+template <bool WRITE, bool ADV>
+__device__ __forceinline__ void block_requests(const NackArgs& a, uint32_t info, const uint32_t* __restrict__ mask, uint32_t b,
                                                uint32_t nd, NackCut cut, uint32_t lane, uint64_t base, uint32_t* out_reqs,
                                                uint32_t* out_items)
 {
-    const uint32_t L = a.item_len, M = a.max_units, flags = REPAIR_SEGMENT | a.info;
+    const uint32_t L = a.item_len, M = a.max_units, flags = REPAIR_SEGMENT | info;
     const uint32_t w_first = cut.lo >> 5, w_last = (cut.hi + 31u) >> 5;  // the words with request bits
     SegVal c_form = {0, 0}, c_since = {0, 0}, c_open = {0, 0};
     uint32_t c_reqs = 0, c_items = 0;
-    auto rword = [&](uint32_t w) { return w >= w_first && w < w_last ? nack_request_word(mask[w], w, cut) : 0u; };
+    auto rword = [&](uint32_t w) {
+        return w >= w_first && w < w_last ? nack_request_word(ADV ? adv_source_word(mask[w]) : mask[w], w, cut) : 0u;
+    };
     for (uint32_t w0 = w_first; w0 < w_last; w0 += 64) {
         const uint32_t w = w0 + lane;
         const uint32_t R = rword(w), Rm = rword(w - 1u), Rp = rword(w + 1u);
@@ -223,8 +190,33 @@ __device__ __forceinline__ void block_requests(const NackArgs& a, const uint32_t
     *out_reqs = c_reqs, *out_items = c_items;
 }
 
+// Where a block's class, its cut and INFO come from.  A NACK: the reception mask and the call's
+// flags.  ADV: the block_repair bit, the repair mask (a.received) and the object word; with the
+// whole object under repair every block is silent and the scan writes the one OBJECT request.
+template <bool ADV>
+__device__ __forceinline__ uint32_t source_info(const NackArgs& a)
+{
+    return ADV ? adv_info(uniform(*a.object)) : a.info;
+}
+template <bool ADV>
+__device__ __forceinline__ BlockShape source_shape(const NackArgs& a, const uint32_t* __restrict__ mask, uint32_t b, uint32_t nd,
+                                                   uint32_t lane)
+{
+    if (!ADV) return block_shape(a.k, a.m, mask, nd, lane);
+    BlockShape r = {NACK_SILENT, {0u, 0u}};
+    if (nd < 1 || nd > a.k || adv_whole_object(uniform(*a.object))) return r;
+    const uint32_t n = nd + a.m, w_end = (n + 31u) >> 5;
+    uint32_t any = 0;
+    for (uint32_t w = lane; w < w_end; w += 64) any |= mask[w] & nack_range_bits(w, 0, n);
+    const bool bit = (uniform(a.block_repair[b >> 5]) >> (b & 31u)) & 1u;
+    r.cls = adv_class(nd, a.k, bit, __any(any != 0u));
+    r.cut = adv_cut(nd, a.m);
+    return r;
+}
+
 // per block: block_start[b][1] = class | the requests of the block's own chain << 8 | its items << 28
 // (a block has at most (k + m + 1) / 2 units of two items: both fit 20 bits)
+template <bool ADV>
 __global__ __launch_bounds__(256) void nack_count_kernel(NackArgs a)
 {
     const uint32_t lane = threadIdx.x & 63u;
@@ -232,9 +224,9 @@ __global__ __launch_bounds__(256) void nack_count_kernel(NackArgs a)
     if (b >= a.nblocks) return;
     const uint32_t nd = a.num_data ? uniform(a.num_data[b]) : a.k;
     const uint32_t* mask = a.received + (uint64_t)b * a.mask_stride;
-    const BlockShape sh = block_shape(a, mask, nd, lane);
+    const BlockShape sh = source_shape<ADV>(a, mask, b, nd, lane);
     uint32_t reqs = 0, items = 0;
-    if (sh.cls == NACK_NEEDING) block_requests<false>(a, mask, b, nd, sh.cut, lane, 0, &reqs, &items);
+    if (sh.cls == NACK_NEEDING) block_requests<false, ADV>(a, source_info<ADV>(a), mask, b, nd, sh.cut, lane, 0, &reqs, &items);
     if (lane == 0) a.rows[2 * (uint64_t)b + 1] = sh.cls | ((uint64_t)reqs << 8) | ((uint64_t)items << 28);
 }
 
@@ -291,6 +283,7 @@ __device__ __forceinline__ uint64_t row_pack(uint32_t cls, bool opens, uint32_t 
 // classes and the forms two bits a block, the units, their item counts and the openers one; the
 // run lengths are walked a second time where the rows are written.  (Each barrier's sums have
 // an array of their own: the next tile's write of it lies behind three other barriers.)
+template <bool ADV>
 __global__ __launch_bounds__(kNackScanThreads) void nack_scan_kernel(NackArgs a)
 {
     constexpr int K = kNackScanItems;
@@ -298,7 +291,8 @@ __global__ __launch_bounds__(kNackScanThreads) void nack_scan_kernel(NackArgs a)
         sums_rest[4][kNackScanWaves];
     __shared__ uint32_t own[kNackScanItems][kNackScanThreads];
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    const uint32_t L = a.item_len, bflags = REPAIR_BLOCK | a.info;
+    const uint32_t info = source_info<ADV>(a);
+    const uint32_t L = a.item_len, bflags = REPAIR_BLOCK | info;
     SegVal c_run[1] = {{0, 0}}, c_form[1] = {{0, 0}}, c_since[1] = {{0, 0}};
     SegVal c_rest[4] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
     for (uint64_t t0 = 0; t0 <= a.nblocks; t0 += kNackScanTile) {
@@ -403,7 +397,13 @@ __global__ __launch_bounds__(kNackScanThreads) void nack_scan_kernel(NackArgs a)
             } else if (i == a.nblocks) {
                 // the last chain's open request is closed by the end of the walk
                 if (form0(j)) put32(a, bytes - (uint64_t)L * items0 - 4u, nack_header_word(form0(j), bflags, L * items0));
-                if (bytes == 0 && a.info && a.nblocks) {  // the INFO-only request (normObject.cpp:1365-1372)
+                if (ADV && adv_whole_object(uniform(*a.object))) {  // one OBJECT request (normSession.cpp:4602, :4662)
+                    NackArgs g = a;
+                    g.first_block_id = 0;
+                    put32(a, 0, nack_header_word(REPAIR_ITEMS, REPAIR_OBJECT, L));
+                    put_item(g, 4, 0, 0, a.k);
+                    bytes = 4u + L, reqs = 1;
+                } else if (bytes == 0 && info && a.nblocks) {  // the INFO-only request (normObject.cpp:1365-1372, :670-681)
                     NackArgs g = a;
                     g.first_block_id = 0;
                     put32(a, 0, nack_header_word(REPAIR_ITEMS, REPAIR_INFO, L));
@@ -421,6 +421,7 @@ __global__ __launch_bounds__(kNackScanThreads) void nack_scan_kernel(NackArgs a)
 }
 
 // per block: its bytes, from block_start[b] on
+template <bool ADV>
 __global__ __launch_bounds__(256) void nack_expand_kernel(NackArgs a)
 {
     const uint32_t lane = threadIdx.x & 63u;
@@ -431,7 +432,8 @@ __global__ __launch_bounds__(256) void nack_expand_kernel(NackArgs a)
     const uint32_t cls = (uint32_t)packed & 3u;
     if (lane == 0 && packed != cls) a.rows[2 * (uint64_t)b + 1] = cls;  // the row's second column is the class again
     if (cls == NACK_SILENT) return;
-    const uint32_t L = a.item_len, bflags = REPAIR_BLOCK | a.info;
+    const uint32_t info = source_info<ADV>(a);
+    const uint32_t L = a.item_len, bflags = REPAIR_BLOCK | info;
     const bool opens = (packed >> 2) & 1u;
     const uint32_t form0 = (uint32_t)(packed >> 3) & 3u, items0 = (uint32_t)(packed >> 8) & 0xffffu;
     const uint32_t run = (uint32_t)(packed >> 32);
@@ -449,22 +451,36 @@ __global__ __launch_bounds__(256) void nack_expand_kernel(NackArgs a)
     }
     const uint32_t nd = a.num_data ? uniform(a.num_data[b]) : a.k;
     const uint32_t* mask = a.received + (uint64_t)b * a.mask_stride;
-    const BlockShape sh = block_shape(a, mask, nd, lane);
+    const NackCut cut = ADV ? adv_cut(nd, a.m) : block_shape(a.k, a.m, mask, nd, lane).cut;
     uint32_t reqs, items;
-    block_requests<true>(a, mask, b, nd, sh.cut, lane, off, &reqs, &items);
+    block_requests<true, ADV>(a, info, mask, b, nd, cut, lane, off, &reqs, &items);
 }
 
 }  // namespace
 
-// (the ABI entry has checked the arguments)
-int launch_nack(const NackArgs& a, hipStream_t s)
+template <bool ADV>
+static int launch_walk(const NackArgs& a, hipStream_t s, const char* what)
 {
     const dim3 grid((a.nblocks + 3u) / 4u);
-    if (a.nblocks) hipLaunchKernelGGL(nack_count_kernel, grid, dim3(256), 0, s, a);
-    hipLaunchKernelGGL(nack_scan_kernel, dim3(1), dim3(kNackScanThreads), 0, s, a);
-    if (a.nblocks) hipLaunchKernelGGL(nack_expand_kernel, grid, dim3(256), 0, s, a);
+    if (a.nblocks) hipLaunchKernelGGL(nack_count_kernel<ADV>, grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(nack_scan_kernel<ADV>, dim3(1), dim3(kNackScanThreads), 0, s, a);
+    if (a.nblocks) hipLaunchKernelGGL(nack_expand_kernel<ADV>, grid, dim3(256), 0, s, a);
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? NFEC_OK : hip_fail(e, "rx_repair_requests launch");
+    return e == hipSuccess ? NFEC_OK : hip_fail(e, what);
+}
+
+// (the ABI entries have checked the arguments)
+int launch_nack(const NackArgs& a, hipStream_t s) { return launch_walk<false>(a, s, "rx_repair_requests launch"); }
+
+// a.received: the sender's repair mask; a.block_repair and a.object: the rest of its state
+int launch_repair_adv(const NackArgs& a, hipStream_t s)
+{
+    if (a.nblocks == 0) {  // (no state to read: the totals and the last row of block_start are zero)
+        NFEC_HIP(hipMemsetAsync(a.totals, 0, 4 * sizeof(uint64_t), s));
+        NFEC_HIP(hipMemsetAsync(a.rows, 0, 2 * sizeof(uint64_t), s));
+        return NFEC_OK;
+    }
+    return launch_walk<true>(a, s, "tx_repair_adv launch");
 }
 
 }  // namespace nfec

@@ -28,6 +28,7 @@
 // object word and clears block_repair behind the blocks' reads of both.
 #include "message_wave.hpp"
 #include "repair_layout.hpp"
+#include "repair_wave.hpp"
 
 namespace nfec {
 
@@ -75,31 +76,6 @@ __device__ __forceinline__ NackWs ws_view(const TxNackArgs& a)
     return w;
 }
 
-// ---- bytes of a message ----
-
-// The four bytes at p, which lie in the message, at any alignment: the aligned dword that holds
-// the first and, when they straddle it, the one behind it; both hold a byte of the message.
-__device__ __forceinline__ uint32_t load32(const uint8_t* __restrict__ p)
-{
-    const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 3u);
-    const uint32_t* __restrict__ q = reinterpret_cast<const uint32_t*>(p - sh);
-    const uint32_t lo = q[0];
-    if (sh == 0) return lo;
-    const uint32_t hi = q[1];
-    return (lo >> (8u * sh)) | (hi << (32u - 8u * sh));
-}
-
-struct WireItem {
-    uint32_t fec_id, object_id, block, symbol;
-};
-// an item of L bytes at p: fec_id, reserved, object id, then the payload ID (nack_layout.hpp)
-__device__ __forceinline__ WireItem load_item(const TxNackArgs& a, const uint8_t* __restrict__ p, uint32_t L)
-{
-    const uint32_t w = load32(p), w0 = load32(p + 4), w1 = L == 12u ? load32(p + 8) : 0u;
-    const RxId id = rx_id_decode(a.id_kind, w0, w1, a.first_block_id);
-    return WireItem{w & 0xffu, bswap16(w >> 16), id.block, id.symbol};
-}
-
 __device__ __forceinline__ SegVal seg_up(SegVal x, uint32_t d) { return SegVal{lane_up(x.v, d), lane_up(x.f, d)}; }
 __device__ __forceinline__ SegVal wave_seg_scan(SegVal x, uint32_t lane)
 {
@@ -121,11 +97,6 @@ __device__ __forceinline__ SegVal seg_behind(SegVal inc, SegVal carry)
 {
     const SegVal last = {(uint64_t)__shfl((unsigned long long)inc.v, 63, 64), (uint32_t)__shfl(inc.f, 63, 64)};
     return seg_combine(carry, last);
-}
-
-__device__ __forceinline__ void add64(uint64_t* p, uint64_t v)
-{
-    if (v) atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
 }
 
 // ---- walk: one wave per message ----
@@ -166,8 +137,8 @@ __global__ __launch_bounds__(256) void tx_nack_walk_kernel(TxNackArgs a)
                 bool bad = false;
                 if (have) {
                     const uint8_t* __restrict__ p = msg + at + 4u + u * step * L;  // (inside the request's rlen bytes)
-                    first = load_item(a, p, L);
-                    last = step == 2u ? load_item(a, p + L, L) : first;
+                    first = load_item(a.id_kind, a.first_block_id, p, L);
+                    last = step == 2u ? load_item(a.id_kind, a.first_block_id, p + L, L) : first;
                     bad = first.fec_id != a.fec_id || last.fec_id != a.fec_id;
                 }
                 // the walk ends at the first item with a foreign fec_id; the units in front of it stand
@@ -250,18 +221,6 @@ __global__ __launch_bounds__(256) void tx_nack_walk_kernel(TxNackArgs a)
         if (n_ignored) atomicAdd(&ws.header->ignored, (unsigned long long)n_ignored);
         if (object_bits) atomicOr(&ws.header->object_bits, object_bits);
     }
-}
-
-// The workgroup's counters into totals[0 .. N): one atomic per counter and workgroup.  (One per
-// block on one address costs more than the blocks' work: 65,536 blocks took 1.4 ms that way.)
-template <int N>
-__device__ __forceinline__ void group_add(uint64_t* totals, const uint64_t (&v)[N], uint32_t lane)
-{
-    __shared__ unsigned long long sums[4][N];
-    if (lane == 0)
-        for (int j = 0; j < N; ++j) sums[threadIdx.x >> 6][j] = v[j];
-    __syncthreads();
-    if (threadIdx.x < (uint32_t)N) add64(totals + threadIdx.x, sums[0][threadIdx.x] + sums[1][threadIdx.x] + sums[2][threadIdx.x] + sums[3][threadIdx.x]);
 }
 
 // ---- apply: one wave per block, the waves striding over the blocks ----

@@ -186,13 +186,16 @@ inline uint32_t nack_block_class_host(const uint32_t* mask, uint32_t nd, uint32_
     *cut = nack_cut(nd, m, e, mth);
     return nack_class(nd, k, e, p, any);
 }
-// A needing block's requests (one chain, flag SEGMENT), block b of the call.
-inline void nack_block_emit_host(const uint32_t* mask, uint32_t nd, NackCut cut, uint32_t b, const NackFormat& f, NackWriter& o)
+// A needing block's requests (one chain, flag SEGMENT), block b of the call.  source(w): word w of
+// what nack_request_word reads, the block's reception mask (or, for an advertisement, the sender's
+// repair mask inverted: suppress_layout.hpp).
+template <class Source>
+inline void nack_block_emit_words(Source source, uint32_t nd, NackCut cut, uint32_t b, const NackFormat& f, NackWriter& o)
 {
     NackChain c;
     uint32_t run = 0;
     for (uint32_t s = cut.lo; s <= cut.hi; ++s) {
-        const bool in = s < cut.hi && ((nack_request_word(mask[s >> 5], s >> 5, cut) >> (s & 31u)) & 1u);
+        const bool in = s < cut.hi && ((nack_request_word(source(s >> 5), s >> 5, cut) >> (s & 31u)) & 1u);
         if (in) {
             ++run;
         } else if (run) {
@@ -201,6 +204,10 @@ inline void nack_block_emit_host(const uint32_t* mask, uint32_t nd, NackCut cut,
         }
     }
     nack_close(o, c, f, REPAIR_SEGMENT);
+}
+inline void nack_block_emit_host(const uint32_t* mask, uint32_t nd, NackCut cut, uint32_t b, const NackFormat& f, NackWriter& o)
+{
+    nack_block_emit_words([mask](uint32_t w) { return mask[w]; }, nd, cut, b, f, o);
 }
 
 // ---- the parser (NormRepairRequest::Unpack, normMessage.cpp:279-305, and ::Iterator, :335-358) ----

@@ -971,6 +971,117 @@ int nfec_tx_end_blocks(const nfec_codec* codec, const uint16_t* num_data, uint32
     return launch_tx_end_blocks(a, static_cast<hipStream_t>(stream));
 }
 
+// ---- NACK suppression and repair advertisements on the device (kernels_suppress.hip, kernels_nack.hip) ----
+static RxRepairState rx_repair_state_view(const nfec_rx_repair_state* state)
+{
+    RxRepairState v;
+    v.repair = state->repair, v.block_repair = state->block_repair, v.object = state->object;
+    return v;
+}
+
+int nfec_rx_handle_repair_content(const nfec_codec* codec, const nfec_rx_messages* messages, uint8_t fec_id, uint8_t fec_m,
+                                  uint16_t object_id, uint32_t first_block_id, const uint32_t* received, uint32_t mask_stride,
+                                  const uint16_t* num_data, uint32_t nblocks, const nfec_rx_repair_state* state, uint64_t* totals,
+                                  void* stream)
+{
+    if (!codec) return fail(NFEC_EINVAL, "null codec");
+    uint32_t id_kind = 0;
+    int rc = rx_content_check(messages, fec_id, fec_m, &id_kind);
+    if (rc || (rc = rx_repair_check(codec->k, codec->m, nblocks, mask_stride, received, state, totals, "rx_handle_repair_content")))
+        return rc;
+    if (primary(codec)->host_only) return host_only_fail();
+    const nfec_codec* c = stripe_for(const_cast<nfec_codec*>(codec), nblocks ? (const void*)state->repair : totals);
+    if (!c) return fail(NFEC_EINVAL, "suppression state is not on a device of the codec");
+    DeviceGuard g(c->device);
+    RxRepairContentArgs a;
+    a.payloads = static_cast<const uint8_t*>(messages->payloads);
+    a.payload_bytes = messages->payload_bytes;
+    a.offsets = messages->offsets;
+    a.length = messages->length;
+    a.count = messages->count;
+    a.count_dev = messages->count_dev;
+    a.id_kind = id_kind;
+    a.fec_id = fec_id;
+    a.object_id = object_id;
+    a.first_block_id = first_block_id;
+    a.received = received;
+    a.mask_stride = mask_stride;
+    a.num_data = num_data;
+    a.k = c->k;
+    a.m = c->m;
+    a.nblocks = nblocks;
+    a.state = rx_repair_state_view(state);
+    a.totals = totals;
+    return launch_rx_repair_content(a, static_cast<hipStream_t>(stream));
+}
+
+int nfec_rx_repair_pending(const nfec_codec* codec, const uint32_t* received, uint32_t mask_stride, const uint16_t* num_data,
+                           uint32_t nblocks, const nfec_rx_repair_state* state, uint32_t flags, uint32_t* pending_blocks,
+                           uint64_t* totals, void* stream)
+{
+    if (!codec) return fail(NFEC_EINVAL, "null codec");
+    int rc = rx_repair_check(codec->k, codec->m, nblocks, mask_stride, received, state, totals, "rx_repair_pending");
+    if (rc) return rc;
+    if (flags & ~(uint32_t)NFEC_NACK_INFO) return fail(NFEC_EINVAL, "rx_repair_pending: unknown flags");
+    if (primary(codec)->host_only) return host_only_fail();
+    const nfec_codec* c = stripe_for(const_cast<nfec_codec*>(codec), nblocks ? (const void*)received : totals);
+    if (!c) return fail(NFEC_EINVAL, "received mask is not on a device of the codec");
+    DeviceGuard g(c->device);
+    RxRepairPendingArgs a;
+    a.received = received;
+    a.mask_stride = mask_stride;
+    a.num_data = num_data;
+    a.k = c->k;
+    a.m = c->m;
+    a.nblocks = nblocks;
+    a.state = rx_repair_state_view(state);
+    a.info_pending = flags & NFEC_NACK_INFO;
+    a.pending_blocks = pending_blocks;
+    a.totals = totals;
+    return launch_rx_repair_pending(a, static_cast<hipStream_t>(stream));
+}
+
+int nfec_tx_repair_adv(const nfec_codec* codec, const nfec_tx_repair_state* state, uint32_t mask_stride, const uint16_t* num_data,
+                       uint32_t nblocks, uint8_t fec_id, uint8_t fec_m, uint16_t object_id, uint32_t first_block_id,
+                       uint32_t max_units, void* content, uint64_t capacity, uint64_t* block_start, uint64_t* totals, void* stream)
+{
+    if (!codec) return fail(NFEC_EINVAL, "null codec");
+    NackFormat f;
+    int rc = nack_format(fec_id, fec_m, object_id, first_block_id, 0, max_units, &f);
+    if (rc) return rc;
+    if ((uint64_t)mask_stride * 32u < (uint64_t)codec->k + codec->m)
+        return fail(NFEC_EINVAL, "tx_repair_adv: mask_stride smaller than (k + m + 31) / 32");
+    if (!block_start || !totals) return fail(NFEC_EINVAL, "null block_start or totals");
+    if (capacity && !content) return fail(NFEC_EINVAL, "null content");
+    if (reinterpret_cast<uintptr_t>(content) & 3u) return fail(NFEC_EINVAL, "content is not 4-byte aligned");
+    if (!state || (nblocks && (!state->repair || !state->block_repair || !state->object)))
+        return fail(NFEC_EINVAL, "tx_repair_adv: null state");
+    if (primary(codec)->host_only) return host_only_fail();
+    const nfec_codec* c = stripe_for(const_cast<nfec_codec*>(codec), nblocks ? (const void*)state->repair : block_start);
+    if (!c) return fail(NFEC_EINVAL, "repair state is not on a device of the codec");
+    DeviceGuard g(c->device);
+    NackArgs a;
+    a.received = state->repair;
+    a.block_repair = state->block_repair;
+    a.object = state->object;
+    a.mask_stride = mask_stride;
+    a.num_data = num_data;
+    a.k = c->k;
+    a.m = c->m;
+    a.nblocks = nblocks;
+    a.id_kind = f.id_kind;
+    a.item_len = f.item_len;
+    a.fec_id = f.fec_id;
+    a.object_id = f.object_id;
+    a.first_block_id = f.first_block_id;
+    a.max_units = f.max_units;
+    a.content = static_cast<uint8_t*>(content);
+    a.capacity = capacity;
+    a.rows = block_start;
+    a.totals = totals;
+    return launch_repair_adv(a, static_cast<hipStream_t>(stream));
+}
+
 // ---- sender assembly on the device (kernels_tx.hip) ----
 // The argument-check order is the receiver entries': arguments first, then the codec's device.
 int nfec_tx_list(const nfec_codec* codec, const uint32_t* pending, uint32_t mask_stride, const uint16_t* num_data,

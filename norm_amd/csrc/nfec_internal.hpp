@@ -864,8 +864,14 @@ struct NackArgs {
     uint64_t capacity = 0;
     uint64_t* rows = nullptr;              // block_start [nblocks + 1][2]
     uint64_t* totals = nullptr;            // [4]
+    // the advertisement only (launch_repair_adv): `received` is the sender's repair mask
+    const uint32_t* block_repair = nullptr;  // [(nblocks + 31) / 32]
+    const uint32_t* object = nullptr;        // [1]: INFO comes from it, not from `info`
 };
 int launch_nack(const NackArgs& a, hipStream_t s);
+// The repair-request content of a NORM_CMD(REPAIR_ADV): the same kernels over the sender's repair
+// state (nfec.h "NACK suppression and repair advertisements on the device").
+int launch_repair_adv(const NackArgs& a, hipStream_t s);
 struct NackFormat;
 // the argument checks the device and the host entry share (nack_host.cpp)
 int nack_format(uint8_t fec_id, uint8_t fec_m, uint16_t object_id, uint32_t first_block_id, uint32_t flags,
@@ -921,6 +927,50 @@ int tx_repair_check(uint32_t k, uint32_t m, uint32_t nblocks, uint32_t mask_stri
                     const char* what);
 int tx_nack_check(const nfec_rx_messages* nacks, uint8_t fec_id, uint8_t fec_m, uint32_t extra_parity, const uint64_t* totals,
                   uint32_t* id_kind);
+
+// NACK suppression on the device (kernels_suppress.hip; nfec.h "NACK suppression and repair
+// advertisements on the device"; suppress_layout.hpp holds the rule).  Handle: one wave per message
+// walks its requests and ORs what they name into the suppression state.  Pending: one wave per
+// word of pending_blocks, a block at a time with the lanes over its mask words.
+struct RxRepairState {
+    uint32_t* repair = nullptr;            // [nblocks][mask_stride]
+    uint32_t* block_repair = nullptr;      // [(nblocks + 31) / 32]
+    uint32_t* object = nullptr;            // [1]
+};
+struct RxRepairContentArgs {
+    const uint8_t* payloads = nullptr;     // the wire buffer
+    uint64_t payload_bytes = 0;
+    const uint64_t* offsets = nullptr;
+    const uint16_t* length = nullptr;
+    uint32_t count = 0;
+    const uint64_t* count_dev = nullptr;   // device, or null: min(count, *count_dev) messages
+    uint32_t id_kind = 0;                  // the payload ID's layout (PAYLOAD_ID_*, rx_parse.hpp)
+    uint32_t fec_id = 0, object_id = 0, first_block_id = 0;
+    const uint32_t* received = nullptr;    // [nblocks][mask_stride], only read
+    uint32_t mask_stride = 0;
+    const uint16_t* num_data = nullptr;    // per block, or null = k
+    uint32_t k = 0, m = 0;
+    uint32_t nblocks = 0;
+    RxRepairState state;
+    uint64_t* totals = nullptr;            // [6]
+};
+int launch_rx_repair_content(const RxRepairContentArgs& a, hipStream_t s);
+struct RxRepairPendingArgs {
+    const uint32_t* received = nullptr;    // [nblocks][mask_stride], only read
+    uint32_t mask_stride = 0;
+    const uint16_t* num_data = nullptr;    // per block, or null = k
+    uint32_t k = 0, m = 0;
+    uint32_t nblocks = 0;
+    RxRepairState state;                   // only read
+    uint32_t info_pending = 0;             // NFEC_NACK_INFO given
+    uint32_t* pending_blocks = nullptr;    // [(nblocks + 31) / 32], or null
+    uint64_t* totals = nullptr;            // [4]
+};
+int launch_rx_repair_pending(const RxRepairPendingArgs& a, hipStream_t s);
+// the argument checks the device and the host entries share (suppress_host.cpp)
+int rx_repair_check(uint32_t k, uint32_t m, uint32_t nblocks, uint32_t mask_stride, const uint32_t* received,
+                    const nfec_rx_repair_state* state, const uint64_t* totals, const char* what);
+int rx_content_check(const nfec_rx_messages* messages, uint8_t fec_id, uint8_t fec_m, uint32_t* id_kind);
 
 // Object segmentation on the device (kernels_obj.hip; nfec.h "object segmentation on the device").
 // One workgroup per run of up to 64 consecutive segments of a block; its lanes stride over the

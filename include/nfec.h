@@ -31,6 +31,10 @@
  *   nfec_tx_list / nfec_tx_emit
  *                         the pending walk, the payload lengths, the FEC payload ID and UnsetPending
  *                         of NormObject::NextSenderMsg  src/common/normObject.cpp:1877-2078
+ *   nfec_tx_emit_data / nfec_rx_ingest_data
+ *                         the same two with the whole NORM_DATA message: the header NextSenderMsg and
+ *                         NormSession::SendMessage write (normObject.cpp:1808-1857, normSession.cpp:4923-4924,
+ *                         :5013) and the validation of NormMsg::InitFromBuffer  src/common/normMessage.cpp:17-92
  *   nfec_tx_handle_nacks / nfec_tx_activate_repairs / nfec_tx_end_blocks
  *                         NormSession::SenderHandleNackMessage (!holdoff)  src/common/normSession.cpp:3706-4300,
  *                         NormBlock::HandleSegmentRequest  src/common/normSegment.cpp:341-402, OnRepairTimeout
@@ -766,6 +770,144 @@ int nfec_tx_repair_adv_host(uint32_t k, uint32_t m, const nfec_tx_repair_state* 
                             const uint16_t* num_data, uint32_t nblocks, uint8_t fec_id, uint8_t fec_m,
                             uint16_t object_id, uint32_t first_block_id, uint32_t max_units, void* content,
                             uint64_t capacity, uint64_t* block_start, uint64_t* totals);
+
+/* ---- NORM_DATA messages on the device ----
+ * nfec_tx_emit and nfec_rx_ingest move payloads and their FEC payload IDs; the host fills and reads
+ * the rest of every header.  This pair moves whole NORM_DATA messages: the sender call writes the
+ * message header, the payload ID, the header extension and the payload, the receiver call takes raw
+ * datagrams by (offset, length) alone, classifies them by NormMsg::InitFromBuffer's rule (reference
+ * src/common/normMessage.cpp:17-92), finds the ID and the payload where the header says they are
+ * and places the payload in the same pass.  It is the layout the reference's default sender uses:
+ * fti_mode FTI_ALWAYS (src/common/normSession.cpp:58) puts the FTI extension between the ID and the
+ * payload of every NORM_DATA (src/common/normObject.cpp:1808-1857).
+ *
+ * A message on the wire (include/normMessage.h:688-696, :769-779, :1183-1186; big-endian fields):
+ *   byte 0          version << 4 | type: version 1, type DATA = 2
+ *   byte 1          hdr_len, the header's length in 32-bit words
+ *   bytes 2-3       sequence
+ *   bytes 4-7       source_id
+ *   bytes 8-9       instance_id
+ *   byte 10         grtt                      byte 11    backoff << 4 | gsize
+ *   byte 12         flags                     byte 13    fec_id
+ *   bytes 14-15     object transport id
+ *   bytes 16 ...    the FEC payload ID (nfec_payload_id_write's bytes: 4, or 8 for fec_id 129)
+ *   ... 4 hdr_len   header extensions; a sender attaches the FTI alone (nfec_fti_write's bytes)
+ *   4 hdr_len ...   the payload
+ * so a header is 20 / 20 / 24 bytes for fec_id 5 / 2 / 129 and 32 / 36 / 40 with the FTI. */
+typedef struct nfec_data_header {      /* the fields one call's messages share */
+    uint32_t source_id;                /* SendMessage: local_node_id (normSession.cpp:5013) */
+    uint16_t instance_id;              /* :4923 */
+    uint16_t first_sequence;           /* message i carries first_sequence + i mod 2^16 (:4924) */
+    uint8_t  grtt, backoff, gsize;     /* quantised, as the session holds them (:1329-1331);
+                                          backoff and gsize are 4-bit fields */
+    uint8_t  flags;                    /* NormObjectMsg::Flag bits, written as given */
+    uint8_t  fec_id, fec_m;
+    uint16_t object_id;
+    uint8_t  ext[16]; uint8_t ext_bytes;   /* 0, or an FTI extension as nfec_fti_write wrote it
+                                              (12 bytes for fec_id 5, 16 for 2 and 129) */
+} nfec_data_header;
+
+/* 16 + nfec_payload_id_length(fec_id) + ext_bytes: the header's bytes, and the `gap` to give
+ * nfec_tx_list.  NFEC_EINVAL for a fec_id other than 2, 5 and 129 and for an ext_bytes that is
+ * neither 0 nor the FTI's length for that fec_id. */
+int nfec_data_header_bytes(uint8_t fec_id, uint8_t ext_bytes);
+
+/* nfec_tx_emit with the whole NORM_DATA header in front of the payload.  segments: nfec_tx_list's
+ * arrays built with gap = H = nfec_data_header_bytes(header->fec_id, header->ext_bytes).  Entry i,
+ * with b, s, len and off as in nfec_tx_emit, writes exactly the bytes [off - H, off + len) of
+ * payloads: the header above with sequence first_sequence + i, hdr_len H / 4 and the payload ID of
+ * (first_block_id + b, s, nd_b), header->ext where ext_bytes > 0, then the slot's first len bytes.
+ * Everything else is nfec_tx_emit's rule: no other byte of payloads is written, or read and written
+ * back; no byte outside the slot's seg_stride is read; with pending given the slot's bit is cleared
+ * by one atomic AND; count_dev bounds the entries.  An entry is rejected, with no byte and no mask
+ * word written, when b >= nblocks, nd_b is outside [1, k], s >= nd_b + m, len > vector_size, off <
+ * H, off + len > payload_bytes or len + H > 65535.  stats (device [2], may be NULL): emitted,
+ * rejected.  msg_offsets_out / msg_length_out (device [count], each may be NULL): off - H and len +
+ * H of entry i, the datagram table a NIC or nfec_rx_ingest_data takes; a rejected entry gets 0 / 0
+ * (a datagram nfec_rx_ingest_data finds unreadable).  NFEC_EINVAL for a fec_id / fec_m pair
+ * nfec_payload_id_write refuses, for a backoff or gsize above 15 and for an ext_bytes
+ * nfec_data_header_bytes refuses; the batch is only read. */
+int nfec_tx_emit_data(const nfec_codec* codec, const nfec_block_batch* batch, const nfec_tx_segments* segments,
+                      const nfec_data_header* header, uint32_t first_block_id, uint32_t* pending,
+                      uint32_t mask_stride, uint64_t* msg_offsets_out, uint16_t* msg_length_out,
+                      uint32_t* stats, void* stream);
+
+typedef struct nfec_data_filter {      /* the sender, code and object one receiver call takes */
+    uint32_t source_id;
+    uint16_t instance_id;
+    uint8_t  fec_id, fec_m;
+    uint16_t object_id;
+} nfec_data_filter;
+
+enum {                                 /* a datagram's class: the first whose condition holds */
+    NFEC_DGRAM_UNREADABLE = 0,         /* off + length > payload_bytes or length < 8: no byte loaded */
+    NFEC_DGRAM_OTHER_TYPE = 1,         /* not NORM_DATA: INFO / CMD / NACK / ACK / REPORT are the host's */
+    NFEC_DGRAM_MALFORMED = 2,          /* InitFromBuffer fails: length < 16 + idlen(byte 13), an unknown
+                                          fec_id byte, 4 hdr_len < 16 + idlen or 4 hdr_len > length */
+    NFEC_DGRAM_OTHER_SENDER = 3,       /* source_id or instance_id is not the filter's */
+    NFEC_DGRAM_OTHER_CODE = 4,         /* the fec_id byte is not the filter's */
+    NFEC_DGRAM_OTHER_OBJECT = 5,       /* the object id is not the filter's */
+    NFEC_DGRAM_REJECTED = 6,           /* from here on nfec_rx_ingest's rule */
+    NFEC_DGRAM_DUPLICATE = 7,
+    NFEC_DGRAM_PLACED = 8,
+    NFEC_DGRAM_CLASSES = 9,
+    NFEC_DGRAM_PARSED = 9              /* nfec_rx_parse_data_host only: past the filter */
+};
+
+/* The receiver intake for raw datagrams.  datagrams->offsets[i] / length[i] are the start and the
+ * length of datagram i in the wire buffer (not of its payload); count_dev as in nfec_rx_ingest.
+ * Each datagram gets one class, above.  For one past the filter the payload ID is read at byte 16
+ * as nfec_rx_ingest reads it, b = (block_id - first_block_id) mod 2^bits, the payload is the bytes
+ * [4 hdr_len, length) (none is a payload of length 0), and nfec_rx_ingest's rule applies: the fec_id
+ * 129 block-length check, one atomic OR for the claim, the payload zero-padded to vector_size and
+ * nothing written into [vector_size, seg_stride).
+ *   - class_out[i] (device uint8 [count], may be NULL): the class.
+ *   - sequence_out[i] (device [count], may be NULL): bytes 2-3, for every readable datagram: the
+ *     host's loss estimator input.
+ *   - block_index_out / symbol_id_out: as in nfec_rx_ingest for a datagram past the filter, all
+ *     ones for any other.
+ *   - stats (device [9], may be NULL; the caller zeroes it): one counter per class, added once per
+ *     wave.
+ *   - totals (device uint64 [1], may be NULL; the caller sets totals[0] to all ones): totals[0]
+ *     becomes the smallest i of a datagram past the filter whose first extension has type 64 (FTI)
+ *     and lies inside the header: the host reads it there (at byte 16 + idlen of the datagram) with
+ *     nfec_fti_read to size a new object.  Only the first extension is examined, and one whose
+ *     length byte is 0 or that runs past 4 hdr_len is not an FTI.
+ *   - Every load from the wire buffer is an aligned chunk of at most 16 bytes that holds at least
+ *     one byte of [off, off + length); a datagram that is not placed loads the chunks of its first
+ *     min(length, 28) bytes and nothing else.
+ * filter->fec_id / fec_m: NFEC_EINVAL for a pair nfec_payload_id_read refuses.  Asynchronous on
+ * stream, on the codec device that holds the batch; owns no codec state; count == 0 or nblocks == 0
+ * launches nothing; null and stride checks as nfec_rx_ingest. */
+int nfec_rx_ingest_data(const nfec_codec* codec, const nfec_block_batch* batch, const nfec_rx_messages* datagrams,
+                        const nfec_data_filter* filter, uint32_t first_block_id, uint32_t* received,
+                        uint32_t mask_stride, uint8_t* class_out, uint16_t* sequence_out,
+                        uint32_t* block_index_out, uint16_t* symbol_id_out, uint32_t* stats, uint64_t* totals,
+                        void* stream);
+
+/* Host twins: no GPU, no codec; the header words and the parse are the kernels' own code.
+ * nfec_data_header_write_host writes the header of message i of a call (sequence first_sequence +
+ * i) for (block_id, symbol, block_len) into out and returns its length; NFEC_EINVAL as
+ * nfec_tx_emit_data, and for a cap below the length. */
+int nfec_data_header_write_host(const nfec_data_header* header, uint32_t i, uint32_t block_id, uint16_t symbol,
+                                uint16_t block_len, void* out, size_t cap);
+/* nfec_rx_ingest_data's parse on host arrays (wire: wire_bytes bytes of host memory).  class_out is
+ * never PLACED, DUPLICATE or REJECTED: a datagram past the filter is NFEC_DGRAM_PARSED, and
+ * nfec_rx_place's rule (with block_len_out for fec_id 129) decides the rest.  For such a datagram
+ * payload_offset_out[i] = off + 4 hdr_len and payload_length_out[i] = length - 4 hdr_len, the
+ * arrays nfec_rx_place and the host-vector paths take; for any other 0 / 0, and block / symbol /
+ * block_len all ones.  sequence_out[i] is written for a readable datagram.  *fti_index_out: the
+ * smallest i with an FTI as first extension, all ones when there is none.  Every output may be
+ * NULL.  Reads no byte outside [off, off + length) of a datagram.  Returns the number of PARSED
+ * datagrams; NFEC_EINVAL and NFEC_ERANGE as nfec_rx_parse_host. */
+int nfec_rx_parse_data_host(const nfec_data_filter* filter, uint32_t first_block_id, const void* wire,
+                            uint64_t wire_bytes, const uint64_t* offsets, const uint16_t* length, uint32_t count,
+                            uint8_t* class_out, uint16_t* sequence_out, uint32_t* block_index_out,
+                            uint16_t* symbol_id_out, uint16_t* block_len_out, uint64_t* payload_offset_out,
+                            uint16_t* payload_length_out, uint64_t* fti_index_out);
+/* The wire-buffer offsets of the aligned 16-byte chunks nfec_rx_ingest_data loads of a datagram at
+ * (off, length) before it knows its class (chunk_out[3]); returns how many (0 for length < 8). */
+int nfec_rx_data_chunks_host(uint64_t off, uint16_t length, uint64_t* chunk_out);
 
 /* ---- object segmentation on the device ----
  * The mapping between a NORM data object (a contiguous run of bytes) and the source slots of its

@@ -29,6 +29,10 @@ REPAIR_SEGMENT, REPAIR_BLOCK, REPAIR_INFO, REPAIR_OBJECT = 1, 2, 4, 8
 NFEC_TX_REPAIR_OBJECT, NFEC_TX_REPAIR_INFO, NFEC_TX_PENDING_INFO = 1, 2, 4
 # nfec_rx_repair_state: the object word
 NFEC_RX_REPAIR_OBJECT, NFEC_RX_REPAIR_INFO = 1, 2
+# nfec_rx_ingest_data / nfec_rx_parse_data_host: a datagram's class
+(NFEC_DGRAM_UNREADABLE, NFEC_DGRAM_OTHER_TYPE, NFEC_DGRAM_MALFORMED, NFEC_DGRAM_OTHER_SENDER, NFEC_DGRAM_OTHER_CODE,
+ NFEC_DGRAM_OTHER_OBJECT, NFEC_DGRAM_REJECTED, NFEC_DGRAM_DUPLICATE, NFEC_DGRAM_PLACED) = range(9)
+NFEC_DGRAM_CLASSES = NFEC_DGRAM_PARSED = 9
 NFEC_FEATURE_RS16_TOEPLITZ, NFEC_FEATURE_RS16_TOEPLITZ2 = 1, 2
 NFEC_OPT_RS16_SHARED_TABLES, NFEC_OPT_RS16_TOEPLITZ_OFF, NFEC_OPT_RS16_TOEPLITZ_ON, NFEC_OPT_HOST_ONLY = 1, 2, 4, 8
 NFEC_OPT_RS16_TOEPLITZ_ONE_LEVEL = 16
@@ -113,6 +117,35 @@ class TxSegments(ctypes.Structure):
         ("length", ctypes.c_void_p),
         ("count", ctypes.c_uint32),
         ("count_dev", ctypes.c_void_p),
+    ]
+
+
+class DataHeader(ctypes.Structure):
+    """nfec_data_header: the NORM_DATA header fields the messages of one call share."""
+    _fields_ = [
+        ("source_id", ctypes.c_uint32),
+        ("instance_id", ctypes.c_uint16),
+        ("first_sequence", ctypes.c_uint16),
+        ("grtt", ctypes.c_uint8),
+        ("backoff", ctypes.c_uint8),
+        ("gsize", ctypes.c_uint8),
+        ("flags", ctypes.c_uint8),
+        ("fec_id", ctypes.c_uint8),
+        ("fec_m", ctypes.c_uint8),
+        ("object_id", ctypes.c_uint16),
+        ("ext", ctypes.c_uint8 * 16),
+        ("ext_bytes", ctypes.c_uint8),
+    ]
+
+
+class DataFilter(ctypes.Structure):
+    """nfec_data_filter: the sender, code and object one receiver call takes."""
+    _fields_ = [
+        ("source_id", ctypes.c_uint32),
+        ("instance_id", ctypes.c_uint16),
+        ("fec_id", ctypes.c_uint8),
+        ("fec_m", ctypes.c_uint8),
+        ("object_id", ctypes.c_uint16),
     ]
 
 
@@ -263,6 +296,15 @@ _SIGS = {
     "nfec_tx_list_host": (_I, [_U32, _U32, _U32, _P, _U32, _P, _U32, _P, _U32, _U32, _P, _P, _P, _P, _U32, _P]),
     "nfec_tx_emit": (_I, [_P, ctypes.POINTER(BlockBatch), ctypes.POINTER(TxSegments), _U8, _U8, _U32, _P, _U32, _P,
                           _P]),
+    "nfec_data_header_bytes": (_I, [_U8, _U8]),
+    "nfec_tx_emit_data": (_I, [_P, ctypes.POINTER(BlockBatch), ctypes.POINTER(TxSegments), ctypes.POINTER(DataHeader), _U32,
+                               _P, _U32, _P, _P, _P, _P]),
+    "nfec_rx_ingest_data": (_I, [_P, ctypes.POINTER(BlockBatch), ctypes.POINTER(RxMessages), ctypes.POINTER(DataFilter),
+                                 _U32, _P, _U32, _P, _P, _P, _P, _P, _P, _P]),
+    "nfec_data_header_write_host": (_I, [ctypes.POINTER(DataHeader), _U32, _U32, _U16, _U16, _P, ctypes.c_size_t]),
+    "nfec_rx_parse_data_host": (_I, [ctypes.POINTER(DataFilter), _U32, _P, _U64, _P, _P, _U32, _P, _P, _P, _P, _P, _P, _P,
+                                     _P]),
+    "nfec_rx_data_chunks_host": (_I, [_U64, _U16, _P]),
     "nfec_tx_handle_nacks": (_I, [_P, ctypes.POINTER(RxMessages), _U8, _U8, _U16, _U32, _P, _U32, _U32, _U32,
                                   ctypes.POINTER(TxRepairStateStruct), _U32, _P, _U64, _P, _P]),
     "nfec_tx_nack_workspace_bytes": (_U64, [_U32, _U32, _U32]),

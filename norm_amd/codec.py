@@ -394,6 +394,95 @@ class _Codec:
                                      pending.shape[1] if pending is not None else 0, _tensor_ptr(stats, "stats"),
                                      _stream_handle(stream)), "nfec_tx_emit")
 
+    # -- NORM_DATA messages on the device (nfec.h, "NORM_DATA messages on the device") --
+    def emit_data_messages(self, blocks, payloads, offsets, block_index, symbol_id, length, header, count_dev=None,
+                           first_block_id=0, pending=None, num_data=None, msg_offsets_out=None, msg_length_out=None,
+                           stats=None, stream=None):
+        """emit_segments with the whole NORM_DATA header in front of every payload (nfec_tx_emit_data).
+        header: data_header(...); the four descriptor tensors are list_pending's, built with gap =
+        data_header_bytes(header.fec_id, header.ext_bytes).  msg_offsets_out int64 / msg_length_out
+        int16: tensors of one element per entry that receive each datagram's start and length (0 / 0
+        for a rejected entry), the table ingest_datagrams takes, or None.  The rest as emit_segments."""
+        self._need()
+        b = _batch_struct(blocks, num_data, False)
+        if pending is not None:
+            _mask_check(pending, blocks.shape[0])
+        count = offsets.numel()
+        given = [(offsets, 8, "offsets"), (block_index, 4, "block_index"), (symbol_id, 2, "symbol_id"),
+                 (length, 2, "length")]
+        given += [(t, size, what) for t, size, what in ((msg_offsets_out, 8, "msg_offsets_out"),
+                                                        (msg_length_out, 2, "msg_length_out")) if t is not None]
+        for t, size, what in given:
+            if t.element_size() != size or t.numel() != count:
+                raise ValueError(f"{what} must hold {count} elements of {size} bytes")
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous CUDA (HIP) tensor")
+        if stats is not None and (stats.element_size() != 4 or stats.numel() < 2):
+            raise ValueError("stats must hold two 32-bit counters")
+        if count_dev is not None and (count_dev.element_size() != 8 or count_dev.numel() < 1 or not count_dev.is_cuda):
+            raise ValueError("count_dev must be a 64-bit CUDA (HIP) tensor")
+        if payloads.element_size() != 1 or not payloads.is_cuda or not payloads.is_contiguous():
+            raise ValueError("payloads must be a contiguous uint8 CUDA (HIP) tensor")
+        seg = N.TxSegments()
+        seg.payloads = payloads.data_ptr() if payloads.numel() else None
+        seg.payload_bytes = payloads.numel()
+        seg.offsets, seg.block_index = offsets.data_ptr(), block_index.data_ptr()
+        seg.symbol_id, seg.length = symbol_id.data_ptr(), length.data_ptr()
+        seg.count = count
+        seg.count_dev = count_dev.data_ptr() if count_dev is not None else None
+        N.check(N.lib().nfec_tx_emit_data(self._h, ctypes.byref(b), ctypes.byref(seg), ctypes.byref(header),
+                                          first_block_id & 0xFFFFFFFF, _tensor_ptr(pending, "pending"),
+                                          pending.shape[1] if pending is not None else 0,
+                                          _tensor_ptr(msg_offsets_out, "msg_offsets_out"),
+                                          _tensor_ptr(msg_length_out, "msg_length_out"), _tensor_ptr(stats, "stats"),
+                                          _stream_handle(stream)), "nfec_tx_emit_data")
+
+    def ingest_datagrams(self, blocks, received, payloads, offsets, length, filter, first_block_id=0, count_dev=None,
+                         num_data=None, class_out=None, sequence_out=None, block_index_out=None, symbol_id_out=None,
+                         stats=None, totals=None, stream=None):
+        """ingest_messages on raw NORM_DATA datagrams (nfec_rx_ingest_data): offsets int64 / length
+        int16 are each datagram's start and length in the wire buffer `payloads`; filter:
+        data_filter(...).  class_out uint8 / sequence_out int16 / block_index_out int32 /
+        symbol_id_out int16: tensors of one element per datagram, or None.  stats: int32 [9], one
+        counter per NFEC_DGRAM_* class (zero it first), or None.  totals: int64 [1] set to -1 by the
+        caller, receives the smallest index of a datagram past the filter that carries an FTI, or
+        None."""
+        self._need()
+        b = _batch_struct(blocks, num_data, False)
+        _mask_check(received, blocks.shape[0])
+        count = offsets.numel()
+        given = [(offsets, 8, "offsets"), (length, 2, "length")]
+        given += [(t, size, what) for t, size, what in ((class_out, 1, "class_out"), (sequence_out, 2, "sequence_out"),
+                                                        (block_index_out, 4, "block_index_out"),
+                                                        (symbol_id_out, 2, "symbol_id_out")) if t is not None]
+        for t, size, what in given:
+            if t.element_size() != size or t.numel() != count:
+                raise ValueError(f"{what} must hold {count} elements of {size} bytes")
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous CUDA (HIP) tensor")
+        if stats is not None and (stats.element_size() != 4 or stats.numel() < N.NFEC_DGRAM_CLASSES):
+            raise ValueError("stats must hold nine 32-bit counters")
+        if totals is not None and (totals.element_size() != 8 or totals.numel() < 1):
+            raise ValueError("totals must hold one 64-bit value")
+        if count_dev is not None and (count_dev.element_size() != 8 or count_dev.numel() < 1 or not count_dev.is_cuda):
+            raise ValueError("count_dev must be a 64-bit CUDA (HIP) tensor")
+        if payloads.element_size() != 1 or not payloads.is_cuda or not payloads.is_contiguous():
+            raise ValueError("payloads must be a contiguous uint8 CUDA (HIP) tensor")
+        msg = N.RxMessages()
+        msg.payloads = payloads.data_ptr() if payloads.numel() else None
+        msg.payload_bytes = payloads.numel()
+        msg.offsets, msg.length = offsets.data_ptr(), length.data_ptr()
+        msg.count = count
+        msg.count_dev = count_dev.data_ptr() if count_dev is not None else None
+        N.check(N.lib().nfec_rx_ingest_data(self._h, ctypes.byref(b), ctypes.byref(msg), ctypes.byref(filter),
+                                            first_block_id & 0xFFFFFFFF, _tensor_ptr(received, "received"),
+                                            received.shape[1], _tensor_ptr(class_out, "class_out"),
+                                            _tensor_ptr(sequence_out, "sequence_out"),
+                                            _tensor_ptr(block_index_out, "block_index_out"),
+                                            _tensor_ptr(symbol_id_out, "symbol_id_out"), _tensor_ptr(stats, "stats"),
+                                            _tensor_ptr(totals, "totals"), _stream_handle(stream)),
+                "nfec_rx_ingest_data")
+
     # -- sender repair state on the device (nfec.h, "sender repair state on the device") --
     def handle_nacks(self, state, payloads, offsets, length, num_data=None, fec_id=5, fec_m=8, object_id=0,
                      first_block_id=0, extra_parity=0, unit_capacity=None, count_dev=None, workspace=None,
@@ -1029,6 +1118,78 @@ def rx_parse_host(fec_id, fec_m, first_block_id, wire, offsets, length):
                                        off.ctypes.data, ln.ctypes.data, off.size, block_index.ctypes.data,
                                        symbol_id.ctypes.data, block_len.ctypes.data), "nfec_rx_parse_host")
     return block_index, symbol_id, block_len
+
+
+def data_header(source_id, instance_id, object_id, fec_id=5, fec_m=8, first_sequence=0, grtt=0, backoff=0, gsize=0,
+                flags=0, fti=None):
+    """nfec_data_header: the fields the NORM_DATA messages of one emit_data_messages call share.
+    fti: the FTI extension's bytes as nfec_fti_write / wire.fti_write gives them (12 for fec_id 5, 16
+    for 2 and 129), attached to every message, or None."""
+    h = N.DataHeader()
+    h.source_id, h.instance_id, h.first_sequence = source_id & 0xFFFFFFFF, instance_id & 0xFFFF, first_sequence & 0xFFFF
+    h.grtt, h.backoff, h.gsize, h.flags = grtt, backoff, gsize, flags
+    h.fec_id, h.fec_m, h.object_id = fec_id, fec_m, object_id & 0xFFFF
+    ext = bytes(fti) if fti is not None else b""
+    if len(ext) > 16:
+        raise ValueError("an FTI extension has 12 or 16 bytes")
+    for j, v in enumerate(ext):
+        h.ext[j] = v
+    h.ext_bytes = len(ext)
+    return h
+
+
+def data_filter(source_id, instance_id, object_id, fec_id=5, fec_m=8):
+    """nfec_data_filter: the sender, code and object ingest_datagrams / rx_parse_data_host take."""
+    f = N.DataFilter()
+    f.source_id, f.instance_id = source_id & 0xFFFFFFFF, instance_id & 0xFFFF
+    f.fec_id, f.fec_m, f.object_id = fec_id, fec_m, object_id & 0xFFFF
+    return f
+
+
+def data_header_bytes(fec_id, ext_bytes=0):
+    """nfec_data_header_bytes: a NORM_DATA header's length, the gap to give list_pending."""
+    return N.check(N.lib().nfec_data_header_bytes(fec_id, ext_bytes), "nfec_data_header_bytes")
+
+
+def data_header_write_host(header, i, block_id, symbol, block_len=0):
+    """nfec_data_header_write_host: the header of message i of a call, as bytes."""
+    out = (ctypes.c_uint8 * 40)()
+    n = N.check(N.lib().nfec_data_header_write_host(ctypes.byref(header), i & 0xFFFFFFFF, block_id & 0xFFFFFFFF, symbol,
+                                                    block_len, out, 40), "nfec_data_header_write_host")
+    return bytes(out[:n])
+
+
+def rx_parse_data_host(filter, first_block_id, wire, offsets, length):
+    """nfec_rx_parse_data_host: what ingest_datagrams reads out of each datagram, on host arrays (no
+    GPU): (class uint8, sequence uint16, block_index uint32, symbol_id uint16, block_len uint16,
+    payload_offset uint64, payload_length uint16, fti_index).  wire: uint8 array; offsets uint64 /
+    length uint16: each datagram's start and length.  A datagram past the filter has class
+    NFEC_DGRAM_PARSED; fti_index is None when no such datagram carries an FTI.  sequence is 0 where
+    the datagram is unreadable."""
+    import numpy as np
+
+    wire = np.ascontiguousarray(wire, np.uint8)
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    length = np.ascontiguousarray(length, np.uint16)
+    n = offsets.size
+    cls, seq = np.zeros(n, np.uint8), np.zeros(n, np.uint16)
+    blk, sym, blen = np.zeros(n, np.uint32), np.zeros(n, np.uint16), np.zeros(n, np.uint16)
+    poff, plen = np.zeros(n, np.uint64), np.zeros(n, np.uint16)
+    fti = ctypes.c_uint64(0)
+    N.check(N.lib().nfec_rx_parse_data_host(ctypes.byref(filter), first_block_id & 0xFFFFFFFF, wire.ctypes.data,
+                                            wire.size, offsets.ctypes.data, length.ctypes.data, n, cls.ctypes.data,
+                                            seq.ctypes.data, blk.ctypes.data, sym.ctypes.data, blen.ctypes.data,
+                                            poff.ctypes.data, plen.ctypes.data, ctypes.addressof(fti)),
+            "nfec_rx_parse_data_host")
+    return cls, seq, blk, sym, blen, poff, plen, (None if fti.value == 0xFFFFFFFFFFFFFFFF else int(fti.value))
+
+
+def rx_data_chunks_host(off, length):
+    """nfec_rx_data_chunks_host: the positions of the aligned 16-byte chunks ingest_datagrams loads of
+    a datagram at (off, length) before it knows its class."""
+    out = (ctypes.c_uint64 * 3)()
+    n = N.lib().nfec_rx_data_chunks_host(off, length, out)
+    return [int(out[c]) for c in range(n)]
 
 
 def repair_max_units(fec_id):

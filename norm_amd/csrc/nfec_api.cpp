@@ -1159,6 +1159,82 @@ int nfec_tx_emit(const nfec_codec* codec, const nfec_block_batch* batch, const n
     return launch_tx_emit(a, static_cast<hipStream_t>(stream));
 }
 
+// ---- NORM_DATA messages on the device (kernels_datamsg.hip) ----
+int nfec_tx_emit_data(const nfec_codec* codec, const nfec_block_batch* batch, const nfec_tx_segments* seg,
+                      const nfec_data_header* header, uint32_t first_block_id, uint32_t* pending, uint32_t mask_stride,
+                      uint64_t* msg_offsets_out, uint16_t* msg_length_out, uint32_t* stats, void* stream)
+{
+    if (!codec || !batch || !seg) return fail(NFEC_EINVAL, "null codec, batch or segments");
+    int rc = pending ? check_mask(codec, pending, mask_stride) : NFEC_OK;
+    if (rc) return rc;
+    if (seg->count && !seg->payloads) return fail(NFEC_EINVAL, "null segments->payloads");
+    if (seg->count && !seg->offsets) return fail(NFEC_EINVAL, "null segments->offsets");
+    if (seg->count && !seg->block_index) return fail(NFEC_EINVAL, "null segments->block_index");
+    if (seg->count && !seg->symbol_id) return fail(NFEC_EINVAL, "null segments->symbol_id");
+    if (seg->count && !seg->length) return fail(NFEC_EINVAL, "null segments->length");
+    TxEmitDataArgs a;
+    if ((rc = data_header_fixed_from(header, a.header))) return rc;
+    if ((rc = check_batch(codec, batch)) || batch->nblocks == 0 || seg->count == 0) return rc;
+    const nfec_codec* c = stripe_for(const_cast<nfec_codec*>(codec), batch->blocks);
+    if (!c) return fail(NFEC_EINVAL, "batch is not on a device of the codec");
+    DeviceGuard g(c->device);
+    a.tx.batch = batch_view(c, batch);
+    a.tx.payloads = static_cast<uint8_t*>(seg->payloads);
+    a.tx.payload_bytes = seg->payload_bytes;
+    a.tx.offsets = seg->offsets;
+    a.tx.block_index = seg->block_index;
+    a.tx.symbol_id = seg->symbol_id;
+    a.tx.length = seg->length;
+    a.tx.count = seg->count;
+    a.tx.count_dev = seg->count_dev;
+    a.tx.id_kind = a.header.id_kind;
+    a.tx.first_block_id = first_block_id;
+    a.tx.pending = pending;
+    a.tx.mask_stride = mask_stride;
+    a.tx.stats = stats;
+    a.msg_offsets_out = msg_offsets_out;
+    a.msg_length_out = msg_length_out;
+    return launch_tx_emit_data(a, static_cast<hipStream_t>(stream));
+}
+
+int nfec_rx_ingest_data(const nfec_codec* codec, const nfec_block_batch* batch, const nfec_rx_messages* msg,
+                        const nfec_data_filter* filter, uint32_t first_block_id, uint32_t* received,
+                        uint32_t mask_stride, uint8_t* class_out, uint16_t* sequence_out, uint32_t* block_index_out,
+                        uint16_t* symbol_id_out, uint32_t* stats, uint64_t* totals, void* stream)
+{
+    if (!codec || !batch || !msg) return fail(NFEC_EINVAL, "null codec, batch or datagrams");
+    int rc = check_mask(codec, received, mask_stride);
+    if (rc) return rc;
+    if (msg->count && !msg->payloads) return fail(NFEC_EINVAL, "null datagrams->payloads");
+    if (msg->count && !msg->offsets) return fail(NFEC_EINVAL, "null datagrams->offsets");
+    if (msg->count && !msg->length) return fail(NFEC_EINVAL, "null datagrams->length");
+    RxIngestDataArgs a;
+    if ((rc = data_filter_from(filter, a.filter))) return rc;
+    if ((rc = check_batch(codec, batch)) || batch->nblocks == 0 || msg->count == 0) return rc;
+    // (the stripe is only read: its shape and its device)
+    const nfec_codec* c = stripe_for(const_cast<nfec_codec*>(codec), batch->blocks);
+    if (!c) return fail(NFEC_EINVAL, "batch is not on a device of the codec");
+    DeviceGuard g(c->device);
+    a.rx.batch = batch_view(c, batch);
+    a.rx.payloads = static_cast<const uint8_t*>(msg->payloads);
+    a.rx.payload_bytes = msg->payload_bytes;
+    a.rx.offsets = msg->offsets;
+    a.rx.length = msg->length;
+    a.rx.count = msg->count;
+    a.rx.count_dev = msg->count_dev;
+    a.rx.id_kind = a.filter.id_kind;
+    a.rx.first_block_id = first_block_id;
+    a.rx.received = received;
+    a.rx.mask_stride = mask_stride;
+    a.rx.block_index_out = block_index_out;
+    a.rx.symbol_id_out = symbol_id_out;
+    a.rx.stats = stats;
+    a.class_out = class_out;
+    a.sequence_out = sequence_out;
+    a.totals = totals;
+    return launch_rx_ingest_data(a, static_cast<hipStream_t>(stream));
+}
+
 // ---- object segmentation on the device (kernels_obj.hip) ----
 // Arguments first, then the codec's device, as above.  The layout is taken only as
 // nfec_object_layout_for makes it: the kernels index the object and the batch by its fields, so a

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/nfec.h"
+#include "data_msg.hpp"
 
 namespace nfec {
 
@@ -844,6 +845,28 @@ struct TxEmitArgs {
     uint32_t* stats = nullptr;             // [2] emitted, rejected (or null)
 };
 int launch_tx_emit(const TxEmitArgs& a, hipStream_t s);
+
+// NORM_DATA messages on the device (kernels_datamsg.hip; nfec.h "NORM_DATA messages on the device";
+// data_msg.hpp holds the header and the parse).  Emit: tx_emit_kernel's shape with the whole message
+// header in front of the payload.  Ingest: rx_ingest_kernel's shape on raw datagrams.
+struct TxEmitDataArgs {
+    TxEmitArgs tx;                         // (id_kind unused: header.id_kind)
+    DataHeaderFixed header;
+    uint64_t* msg_offsets_out = nullptr;   // [count], or null
+    uint16_t* msg_length_out = nullptr;    // [count], or null
+};
+int launch_tx_emit_data(const TxEmitDataArgs& a, hipStream_t s);
+struct RxIngestDataArgs {
+    RxIngestArgs rx;                       // (id_kind unused: filter.id_kind; stats: [9], one per class)
+    DataFilter filter;
+    uint8_t* class_out = nullptr;          // [count], or null
+    uint16_t* sequence_out = nullptr;      // [count], or null
+    uint64_t* totals = nullptr;            // [1], or null
+};
+int launch_rx_ingest_data(const RxIngestDataArgs& a, hipStream_t s);
+// the caller's structs into the kernels' constants, with the checks the host twins share (data_msg_host.cpp)
+int data_header_fixed_from(const nfec_data_header* h, DataHeaderFixed& f);
+int data_filter_from(const nfec_data_filter* in, DataFilter& f);
 
 // Repair requests on the device (kernels_nack.hip; nfec.h "repair requests on the device").  The
 // shape of the transmission list: per-block classes, bytes and requests (one wave per block) into

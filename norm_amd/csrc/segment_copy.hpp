@@ -1,6 +1,7 @@
 // segment_copy.hpp -- the two misaligned-copy rules of the device sender, receiver and object paths,
 // one 16-byte piece at a time.  Shared by the kernels (kernels_rx.hip, kernels_tx.hip,
-// kernels_obj.hip) and a host driver (tests/native/segment_copy_asan.cpp) that runs the same
+// kernels_obj.hip, kernels_stream.hip, kernels_datamsg.hip) and host drivers
+// (tests/native/segment_copy_asan.cpp; data_msg_asan.cpp for the header form) that run the same
 // arithmetic under AddressSanitizer with everything outside the permitted bytes unaddressable: what
 // the comments below claim about loads and stores is what that driver checks.
 #pragma once
@@ -167,15 +168,11 @@ NFEC_SC_HD uint32_t scatter_pieces(const uint8_t* dst, uint32_t total)
     return total ? ((uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u) + total + 15u) >> 4 : 0u;
 }
 
-// piece p of the message; no store when the message has no piece p
-NFEC_SC_HD void scatter_piece(uint8_t* __restrict__ dst, const uint8_t* __restrict__ slot, uint32_t len, uint64_t id,
-                              uint32_t idlen, uint32_t p)
+// The slot's bytes of piece p, in place, for a message whose slot byte 0 lies q bytes into piece 0
+// (q = dst mod 16 + the bytes in front of the payload): piece p holds slot bytes [16 (p - pb) + sh,
+// + 16).  The bytes of o[] that are not the slot's are zero or arbitrary.
+NFEC_SC_HD void scatter_slot_bytes(const uint8_t* __restrict__ slot, uint32_t len, uint32_t q, uint32_t p, uint32_t (&o)[4])
 {
-    const uint32_t total = idlen + len;
-    if (p >= scatter_pieces(dst, total)) return;
-    const uint32_t dres = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u);
-    // slot byte 0 lies q bytes into piece 0: piece p holds slot bytes [16 (p - pb) + sh, + 16)
-    const uint32_t q = dres + idlen;
     const int32_t pb = (int32_t)((q + 15u) >> 4);
     const uint32_t sh = (0u - q) & 15u;
     const uint32_t dsh = (sh >> 2) & 1u, bsh = sh & 3u;
@@ -191,21 +188,16 @@ NFEC_SC_HD void scatter_piece(uint8_t* __restrict__ dst, const uint8_t* __restri
         if (8 * c < need_hi && 8 * c + 8 > need_lo) v = __builtin_nontemporal_load(chunk + c);
         e[2 * j] = v[0], e[2 * j + 1] = v[1];
     }
-    uint32_t o[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) o[j] = alignbyte(dsh ? e[j + 2] : e[j + 1], dsh ? e[j + 1] : e[j], bsh);
+}
+
+// Piece p's own bytes of o[] to the destination: all 16 where the message covers the piece, else
+// as dwords where a whole dword is the message's and as bytes elsewhere.  total: the message's bytes.
+NFEC_SC_HD void scatter_store(uint8_t* __restrict__ dst, uint32_t total, uint32_t p, const uint32_t (&o)[4])
+{
+    const uint32_t dres = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u);
     const uint32_t first = p * 16u;  // the piece's first byte, counted from piece 0
-    if (first < q) {
-        // the piece may hold ID bytes: byte t of it is message byte first + t - dres
-#pragma unroll
-        for (int w = 0; w < 4; ++w)
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const uint32_t j = first + 4u * w + t - dres;  // (wraps below the message: j >= idlen)
-                if (j < idlen) o[w] = (o[w] & ~(0xffu << (8 * t))) | ((uint32_t)((id >> (8u * j)) & 0xffu) << (8 * t));
-            }
-    }
-    // the piece's own bytes [lo, hi)
     const uint32_t lo = p == 0 ? dres : 0u;
     const uint32_t hi = dres + total - first < 16u ? dres + total - first : 16u;
     uint8_t* d = dst - dres + first;
@@ -224,6 +216,97 @@ NFEC_SC_HD void scatter_piece(uint8_t* __restrict__ dst, const uint8_t* __restri
             }
         }
     }
+}
+
+// piece p of the message; no store when the message has no piece p
+NFEC_SC_HD void scatter_piece(uint8_t* __restrict__ dst, const uint8_t* __restrict__ slot, uint32_t len, uint64_t id,
+                              uint32_t idlen, uint32_t p)
+{
+    const uint32_t total = idlen + len;
+    if (p >= scatter_pieces(dst, total)) return;
+    const uint32_t dres = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u);
+    const uint32_t q = dres + idlen;  // slot byte 0 lies q bytes into piece 0
+    uint32_t o[4];
+    scatter_slot_bytes(slot, len, q, p, o);
+    const uint32_t first = p * 16u;  // the piece's first byte, counted from piece 0
+    if (first < q) {
+        // the piece may hold ID bytes: byte t of it is message byte first + t - dres
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const uint32_t j = first + 4u * w + t - dres;  // (wraps below the message: j >= idlen)
+                if (j < idlen) o[w] = (o[w] & ~(0xffu << (8 * t))) | ((uint32_t)((id >> (8u * j)) & 0xffu) << (8 * t));
+            }
+    }
+    scatter_store(dst, total, p, o);
+}
+
+// ---- scatter behind a message header of up to 40 bytes (a NORM_DATA header, data_msg.hpp) ----
+//
+// The same rule with `hlen` header bytes (a multiple of 4) in front of the payload instead of an
+// ID of at most 8.  The header is given as words (byte j of the header in bits [8 (j mod 4), + 8) of
+// hdr[j / 4]; words past hlen / 4 are zero), the same for every lane of a wave.  It reaches into
+// pieces 0 .. 3 at the most (15 + 40 bytes), so it is first brought to where it lies in those four
+// pieces -- img[i] is bytes [4i, 4i + 4) of pieces 0 .. 3, header byte j at byte dst mod 16 + j --
+// by one byte funnel and a dword shift that are uniform where dst is, with no indexing by a lane's
+// value; a lane then picks its piece's four words of the image by selects.
+constexpr uint32_t kScatterHeaderWords = 10;
+
+NFEC_SC_HD void scatter_header_image(const uint32_t (&hdr)[kScatterHeaderWords], uint32_t dres, uint32_t (&img)[16])
+{
+    const uint32_t ds = dres >> 2, bs = dres & 3u;
+    // pre[k]: header bytes [4k - bs, 4k - bs + 4) (zero in front of and behind the header)
+    uint32_t pre[kScatterHeaderWords + 1];
+#pragma unroll
+    for (uint32_t k = 0; k <= kScatterHeaderWords; ++k) {
+        const uint32_t cur = k < kScatterHeaderWords ? hdr[k] : 0u, prev = k ? hdr[k - 1] : 0u;
+        pre[k] = alignbyte(cur, bs ? prev : cur, (4u - bs) & 3u);
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < 16; ++i) img[i] = 0u;
+    switch (ds) {
+    case 0:
+#pragma unroll
+        for (uint32_t k = 0; k <= kScatterHeaderWords; ++k) img[k] = pre[k];
+        break;
+    case 1:
+#pragma unroll
+        for (uint32_t k = 0; k <= kScatterHeaderWords; ++k) img[k + 1] = pre[k];
+        break;
+    case 2:
+#pragma unroll
+        for (uint32_t k = 0; k <= kScatterHeaderWords; ++k) img[k + 2] = pre[k];
+        break;
+    default:
+#pragma unroll
+        for (uint32_t k = 0; k <= kScatterHeaderWords; ++k) img[k + 3] = pre[k];
+        break;
+    }
+}
+
+// piece p of the message [dst, dst + hlen + len): the header, then the slot's first len bytes; no
+// store when the message has no piece p.  img: scatter_header_image of the header at dst mod 16.
+NFEC_SC_HD void scatter_piece_header(uint8_t* __restrict__ dst, const uint8_t* __restrict__ slot, uint32_t len,
+                                     const uint32_t (&img)[16], uint32_t hlen, uint32_t p)
+{
+    const uint32_t total = hlen + len;
+    if (p >= scatter_pieces(dst, total)) return;
+    const uint32_t dres = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u);
+    const uint32_t q = dres + hlen;  // slot byte 0 lies q bytes into piece 0
+    uint32_t o[4];
+    scatter_slot_bytes(slot, len, q, p, o);
+    const uint32_t first = p * 16u;
+    if (first < q) {
+        // the piece holds header bytes: those of its bytes that lie below q (p <= 3 here)
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const uint32_t hv = p == 0 ? img[w] : p == 1 ? img[4 + w] : p == 2 ? img[8 + w] : img[12 + w];
+            const uint32_t m = low_bytes((int32_t)q - (int32_t)(first + 4u * w));
+            o[w] = (o[w] & ~m) | (hv & m);
+        }
+    }
+    scatter_store(dst, total, p, o);
 }
 
 }  // namespace nfec

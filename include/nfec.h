@@ -909,6 +909,194 @@ int nfec_rx_parse_data_host(const nfec_data_filter* filter, uint32_t first_block
  * (off, length) before it knows its class (chunk_out[3]); returns how many (0 for length < 8). */
 int nfec_rx_data_chunks_host(uint64_t off, uint16_t length, uint64_t* chunk_out);
 
+/* ---- NORM_NACK and NORM_CMD(REPAIR_ADV) messages on the device ----
+ * nfec_rx_repair_requests and nfec_tx_repair_adv produce repair-request content, nfec_tx_handle_nacks
+ * and nfec_rx_handle_repair_content consume it.  These calls are the messages in between: a
+ * receiver's content cut into NORM_NACK messages of at most segment_size content bytes each, the
+ * sender's content behind a NORM_CMD(REPAIR_ADV) header, and on the far side the intake that tells
+ * NACKs and advertisements from everything else in a receive buffer and finds their content.  With
+ * them "reception masks -> NACKs on the wire -> sender repair state" and "sender state -> REPAIR_ADV
+ * on the wire -> receiver suppression state" run on one stream without a synchronize.
+ *
+ * NORM_NACK on the wire (include/normMessage.h:1906-1989; big-endian fields), 24-byte base header:
+ *   byte 0          version << 4 | type = 0x14      byte 1    hdr_len in 32-bit words
+ *   bytes 2-3       sequence
+ *   bytes 4-7       source_id (the receiver)
+ *   bytes 8-11      sender_id
+ *   bytes 12-13     instance_id                     bytes 14-15   reserved, 0
+ *   bytes 16-19     grtt_response seconds           bytes 20-23   grtt_response microseconds
+ *   ... 4 hdr_len   an optional header extension
+ *   4 hdr_len ...   the repair-request content
+ * NORM_CMD(REPAIR_ADV) (:1200-1249, :1688-1737), 16-byte base header:
+ *   byte 0          0x13                            byte 1    hdr_len
+ *   bytes 2-3       sequence
+ *   bytes 4-7       source_id
+ *   bytes 8-9       instance_id
+ *   byte 10         grtt                            byte 11   backoff << 4 | gsize
+ *   byte 12         flavor = 5                      byte 13   flags (NORM_REPAIR_ADV_FLAG_LIMIT = 1)
+ *   bytes 14-15     reserved, 0
+ *   then the extension and the content as in the NACK.
+ * The only extension a sender of either message attaches is the 12-byte CC-feedback extension
+ * (NormCCFeedbackExtension, :1741-1807); the caller supplies it as opaque bytes. */
+typedef struct nfec_nack_header {      /* the fields one call's NACKs share */
+    uint32_t source_id;                /* the receiver: local_node_id (normSession.cpp:5013) */
+    uint32_t sender_id;                /* the sender the NACK is for */
+    uint16_t instance_id;              /* the sender's instance */
+    uint16_t first_sequence;           /* message i carries first_sequence + i * sequence_step */
+    uint16_t sequence_step;            /* 0: every NACK carries first_sequence, as the reference
+                                          sends all of them with 0 (normSession.cpp:4958) */
+    uint32_t grtt_response_sec;        /* the sender's send time as the receiver echoes it */
+    uint32_t grtt_response_usec;
+    uint8_t  ext[12]; uint8_t ext_bytes;   /* 0, or a 12-byte CC-feedback extension */
+} nfec_nack_header;
+
+typedef struct nfec_adv_header {       /* the header of one NORM_CMD(REPAIR_ADV) */
+    uint32_t source_id;                /* the sender */
+    uint16_t instance_id;
+    uint16_t sequence;
+    uint8_t  grtt, backoff, gsize;     /* quantised, as the session holds them; backoff and gsize
+                                          are 4-bit fields */
+    uint8_t  ext[12]; uint8_t ext_bytes;   /* 0, or a 12-byte CC-feedback extension */
+} nfec_adv_header;
+
+/* 24 + ext_bytes and 16 + ext_bytes; NFEC_EINVAL for an ext_bytes other than 0 and 12. */
+int nfec_nack_header_bytes(uint8_t ext_bytes);
+int nfec_adv_header_bytes(uint8_t ext_bytes);
+
+/* The cut rule: NormSenderNode::FragmentNack (src/common/normNode.cpp:2676-2772), which turns content
+ * that exceeds one message into several (OnRepairTimeout, :2601-2610), with two departures.  With S =
+ * segment_size, L = 4 + nfec_payload_id_length(fec_id) the item length, U the unit length of a
+ * request (2 L for form RANGES, L for any other), P the content bytes in the open message and len a
+ * request's length (4 + its item bytes), for each request in order:
+ *   A. P + len <= S: the request is copied whole.
+ *   B. otherwise, if the request has at least one unit and P + 4 + U <= S, it is split: a copy of its
+ *      4-byte header (form, flags, and the length of the units that follow it in this message), then
+ *      units while they fit; whenever the next unit does not fit (P + U > S) the message is closed and
+ *      a new one opens with another copy of the header (P = 4).  The message that holds the request's
+ *      last unit stays open.
+ *   C. otherwise the message is closed, P = 0, and the same request is examined again.
+ * Departure 1: in arm C the reference advances past the request it could not place and never sends
+ * it (:2699-2702, :2756-2762).  Departure 2: the reference enters arm B on P + 4 < S alone and so can
+ * end a message with a request header that has no items.  Where neither situation occurs the bytes
+ * are the reference's; where everything fits, the one message is the content itself.
+ * The walk stops at a request header that does not fit, at a length that runs past the content, at
+ * item bytes that are not a multiple of L and at a RANGES request with an odd item count; what
+ * precedes the stop stands.  (Items are not examined: a foreign fec_id, at which
+ * nfec_repair_parse_host stops, is the consumer's to refuse.)  A request without items is legal: it
+ * is copied when it fits, else arm C applies.
+ * NFEC_EINVAL for a segment_size that is not a multiple of 4, below 4 + 2 L (the reference's loop
+ * would not advance) or with segment_size + header bytes > 65535.
+ *
+ * nfec_nack_fragment writes whole NORM_NACK messages.  content: device, 4-byte aligned; the call
+ * reads min(content_capacity, *content_bytes_dev) bytes of it, content_bytes_dev (device) being
+ * totals[0] of the producing nfec_rx_repair_requests as it lies in HBM.  Message i is at wire + i *
+ * pitch (wire: device, 4-byte aligned, wire_bytes bytes; pitch a multiple of 4, at least H +
+ * segment_size with H = nfec_nack_header_bytes(header->ext_bytes)): the header with sequence
+ * first_sequence + i * sequence_step, then its content by the rule above.  msg_offsets_out[i] = i *
+ * pitch and msg_length_out[i] (device [capacity], each may be NULL) are the datagram table.  Only
+ * the first min(capacity, wire_bytes / pitch) messages are written; no byte of wire outside a
+ * message's own [i * pitch, i * pitch + length_i) is stored, or read and written back.
+ * totals: device uint64 [6] = {messages, content bytes written (the messages' lengths without their
+ * headers), requests read, requests split by arm B, content bytes consumed, 1 if cut short: the walk
+ * stopped before the end of the content, or *content_bytes_dev exceeds content_capacity}: the full
+ * numbers even past capacity.  totals[0] is what a consumer's nfec_rx_messages.count_dev points at.
+ * block_start (device, may be NULL with nblocks 0) is the array the producing call wrote for the same
+ * content: by that call's rule the bytes emitted at a needing block's position begin a chain and so
+ * a request, and what follows them begins another, so offset 0 and both ends of every class-1 row are
+ * request boundaries and the request headers between two of them are walked by one lane each.
+ * Without the hint the call is correct but one lane walks every request header of the content: slow
+ * (about 100 ms for 140,000 requests, measured; more than cutting on the host costs).  Every load is bounds-checked against the content
+ * length: a hint that does not belong to the content yields unspecified messages but no access
+ * outside the buffers.  workspace: device, 8-byte aligned, at least nfec_nack_fragment_workspace_bytes(
+ * content_capacity, nblocks) bytes, the call's until it has run.  NFEC_ERANGE for a content_capacity
+ * of 2^32 or more.  Asynchronous on stream, on the codec device that holds the content; owns no codec
+ * state; the content is only read. */
+int nfec_nack_fragment(const nfec_codec* codec, const void* content, uint64_t content_capacity,
+                       const uint64_t* content_bytes_dev, const uint64_t* block_start, uint32_t nblocks,
+                       uint8_t fec_id, uint32_t segment_size, const nfec_nack_header* header, void* wire,
+                       uint64_t wire_bytes, uint32_t pitch, uint64_t* msg_offsets_out, uint16_t* msg_length_out,
+                       uint32_t capacity, uint64_t* totals, void* workspace, uint64_t workspace_bytes,
+                       void* stream);
+uint64_t nfec_nack_fragment_workspace_bytes(uint64_t content_capacity, uint32_t nblocks);
+
+/* One NORM_CMD(REPAIR_ADV) at wire (device, 4-byte aligned, wire_bytes >= H + segment_size with H =
+ * nfec_adv_header_bytes(header->ext_bytes)): the header, then the first message of the same cut of
+ * content (nfec_tx_repair_adv's, content_bytes_dev its totals[0]).  The flags byte has
+ * NORM_REPAIR_ADV_FLAG_LIMIT set exactly when content remained; the reference leaves the flag "TBD"
+ * (normSession.cpp:4646) and silently truncates.  Where everything fits the bytes are the
+ * reference's.  msg_length_out (device uint16 [1]): the message's length, 0 for empty content, of
+ * which nothing is written.  totals: device uint64 [3] = {content bytes written, content bytes left
+ * out, limit flag}.  One wave walks the request headers of the first message (at most segment_size /
+ * 4).  Asynchronous on stream; owns no codec state. */
+int nfec_tx_repair_adv_message(const nfec_codec* codec, const void* content, uint64_t content_capacity,
+                               const uint64_t* content_bytes_dev, uint8_t fec_id, uint32_t segment_size,
+                               const nfec_adv_header* header, void* wire, uint64_t wire_bytes,
+                               uint16_t* msg_length_out, uint64_t* totals, void* stream);
+
+#define NFEC_CTL_ANY_INSTANCE 1u   /* filter flags: do not test instance_id (the reference's sender
+                                      tests the id alone, normSession.cpp:2964) */
+#define NFEC_CTL_TAKE_NACK    2u   /* give NACKs content entries (a sender's intake) */
+#define NFEC_CTL_TAKE_ADV     4u   /* give REPAIR_ADVs content entries (a receiver's intake) */
+typedef struct nfec_ctl_filter {
+    uint32_t sender_id;                /* NACK: its sender_id field; CMD: its source_id */
+    uint16_t instance_id;
+    uint32_t local_id;                 /* messages from this node are its own; 0: no such test */
+    uint32_t flags;                    /* NFEC_CTL_* */
+} nfec_ctl_filter;
+
+enum {                                 /* a control datagram's class: the first whose condition holds */
+    NFEC_CTL_UNREADABLE = 0,           /* as NFEC_DGRAM_UNREADABLE: no byte loaded */
+    NFEC_CTL_OTHER_TYPE = 1,           /* neither NORM_NACK (4) nor NORM_CMD (3) */
+    NFEC_CTL_MALFORMED = 2,            /* InitFromBuffer fails (normMessage.cpp:17-92): length or 4 hdr_len
+                                          below 24 (NACK) / 16 (CMD), or 4 hdr_len > length */
+    NFEC_CTL_OTHER_FLAVOR = 3,         /* a CMD that is not REPAIR_ADV (5) */
+    NFEC_CTL_OWN = 4,                  /* source_id == local_id (normSession.cpp:2816-2817) */
+    NFEC_CTL_OTHER_SENDER = 5,         /* NACK: sender_id, CMD: source_id is not the filter's */
+    NFEC_CTL_OTHER_INSTANCE = 6,       /* instance_id is not the filter's (not under ANY_INSTANCE) */
+    NFEC_CTL_NACK = 7,
+    NFEC_CTL_REPAIR_ADV = 8,
+    NFEC_CTL_CLASSES = 9,
+    NFEC_CTL_EXTENDED = 0x80           /* class_out's top bit (classes 7 and 8): 4 hdr_len exceeds the
+                                          base header, an extension is there for the host to read */
+};
+
+/* The intake for control datagrams: datagrams as in nfec_rx_ingest_data.  Each gets one class,
+ * above.  For a NACK under NFEC_CTL_TAKE_NACK and a REPAIR_ADV under NFEC_CTL_TAKE_ADV
+ * content_offset_out[i] = off + 4 hdr_len and content_length_out[i] = length - 4 hdr_len; every
+ * other datagram gets 0 / 0, which is a readable, empty message to nfec_tx_handle_nacks and
+ * nfec_rx_handle_repair_content: the tables are index-aligned with the datagrams, so arrival order,
+ * which nfec_tx_handle_nacks depends on, is kept, and they go into an nfec_rx_messages as they are.
+ * class_out (device uint8 [count]), source_id_out (device uint32 [count]: bytes 4-7 of a readable
+ * datagram, 0 for an unreadable one) and grtt_response_out (device uint32 [count][2]: seconds, microseconds of a NACK; 0 / 0
+ * for any other) may be NULL; content_offset_out (uint64 [count]) and content_length_out (uint16
+ * [count]) may not.  stats (device uint32 [9], may be NULL; the caller zeroes it): one counter per
+ * class.  A CC extension is left in place for the host.  Every load from the wire buffer is an
+ * aligned chunk of at most 16 bytes that holds at least one byte of the datagram's first min(length,
+ * 24) bytes.  Outputs past min(count, *count_dev) keep their bytes.  Asynchronous on stream, on the
+ * codec device that holds the wire buffer; owns no codec state; count == 0 launches nothing. */
+int nfec_rx_ingest_control(const nfec_codec* codec, const nfec_rx_messages* datagrams, const nfec_ctl_filter* filter,
+                           uint8_t* class_out, uint64_t* content_offset_out, uint16_t* content_length_out,
+                           uint32_t* source_id_out, uint32_t* grtt_response_out, uint32_t* stats, void* stream);
+
+/* Host twins: no GPU, no codec; the cut, the header words and the parse are the kernels' own code
+ * (content and wire in host memory at any alignment).
+ * nfec_nack_fragment_host: nfec_nack_fragment on host arrays, `bytes` the content's length.
+ * nfec_nack_header_write_host: the header of message i of a call into out; returns its length.
+ * nfec_adv_message_host: nfec_tx_repair_adv_message; returns the message's length.
+ * nfec_ctl_parse_host: nfec_rx_ingest_control's outputs, stats included (added to); reads no byte
+ * outside a datagram's first min(length, 24) bytes; returns the number of datagrams that got a
+ * content entry. */
+int nfec_nack_fragment_host(const void* content, uint64_t bytes, uint8_t fec_id, uint32_t segment_size,
+                            const nfec_nack_header* header, void* wire, uint64_t wire_bytes, uint32_t pitch,
+                            uint64_t* msg_offsets_out, uint16_t* msg_length_out, uint32_t capacity, uint64_t* totals);
+int nfec_nack_header_write_host(const nfec_nack_header* header, uint32_t i, void* out, size_t cap);
+int nfec_adv_message_host(const void* content, uint64_t bytes, uint8_t fec_id, uint32_t segment_size,
+                          const nfec_adv_header* header, void* wire, uint64_t wire_bytes, uint64_t* totals);
+int nfec_ctl_parse_host(const nfec_ctl_filter* filter, const void* wire, uint64_t wire_bytes, const uint64_t* offsets,
+                        const uint16_t* length, uint32_t count, uint8_t* class_out, uint64_t* content_offset_out,
+                        uint16_t* content_length_out, uint32_t* source_id_out, uint32_t* grtt_response_out,
+                        uint32_t* stats);
+
 /* ---- object segmentation on the device ----
  * The mapping between a NORM data object (a contiguous run of bytes) and the source slots of its
  * FEC blocks: one step before nfec_encode on the sender, one step after nfec_decode_received on

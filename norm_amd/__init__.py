@@ -9,7 +9,10 @@ from ._native import (NFEC_RS8, NFEC_RS16, NFEC_MDP, NFEC_ACCUMULATE, NFEC_FEATU
                       NFEC_STREAM_EOM, NFEC_STREAM_FLUSH, NFEC_STREAM_END, NFEC_NACK_INFO, NFEC_TX_REPAIR_OBJECT, NFEC_TX_REPAIR_INFO,
                       NFEC_TX_PENDING_INFO, NFEC_DGRAM_UNREADABLE, NFEC_DGRAM_OTHER_TYPE, NFEC_DGRAM_MALFORMED,
                       NFEC_DGRAM_OTHER_SENDER, NFEC_DGRAM_OTHER_CODE, NFEC_DGRAM_OTHER_OBJECT, NFEC_DGRAM_REJECTED,
-                      NFEC_DGRAM_DUPLICATE, NFEC_DGRAM_PLACED, NFEC_DGRAM_CLASSES, NFEC_DGRAM_PARSED, NfecError, lib)
+                      NFEC_DGRAM_DUPLICATE, NFEC_DGRAM_PLACED, NFEC_DGRAM_CLASSES, NFEC_DGRAM_PARSED, NFEC_CTL_UNREADABLE,
+                      NFEC_CTL_OTHER_TYPE, NFEC_CTL_MALFORMED, NFEC_CTL_OTHER_FLAVOR, NFEC_CTL_OWN, NFEC_CTL_OTHER_SENDER,
+                      NFEC_CTL_OTHER_INSTANCE, NFEC_CTL_NACK, NFEC_CTL_REPAIR_ADV, NFEC_CTL_CLASSES, NFEC_CTL_EXTENDED,
+                      NFEC_CTL_ANY_INSTANCE, NFEC_CTL_TAKE_NACK, NFEC_CTL_TAKE_ADV, NfecError, lib)
 from .codec import (  # noqa: F401
     NormEncoderRS8, NormDecoderRS8, NormEncoderRS16, NormDecoderRS16, NormEncoderMDP, NormDecoderMDP,
     BlockLayout, build_generator, device_count, fill_blocks, make_erasures, stream_copy, zero_erasures,
@@ -18,7 +21,8 @@ from .codec import (  # noqa: F401
     StreamState, stream_frame_host, TxRepairState, tx_repair_state, tx_handle_nacks_host, tx_activate_repairs_host,
     tx_end_blocks_host, RxRepairState, rx_repair_state, rx_handle_repair_content_host, rx_repair_pending_host,
     tx_repair_adv_host, data_header, data_filter, data_header_bytes, data_header_write_host, rx_parse_data_host,
-    rx_data_chunks_host,
+    rx_data_chunks_host, nack_header, adv_header, ctl_filter, nack_header_bytes, adv_header_bytes,
+    nack_header_write_host, nack_fragment_host, adv_message_host, ctl_parse_host,
 )
 
 __version__ = "0.1.0"

@@ -33,6 +33,12 @@ NFEC_RX_REPAIR_OBJECT, NFEC_RX_REPAIR_INFO = 1, 2
 (NFEC_DGRAM_UNREADABLE, NFEC_DGRAM_OTHER_TYPE, NFEC_DGRAM_MALFORMED, NFEC_DGRAM_OTHER_SENDER, NFEC_DGRAM_OTHER_CODE,
  NFEC_DGRAM_OTHER_OBJECT, NFEC_DGRAM_REJECTED, NFEC_DGRAM_DUPLICATE, NFEC_DGRAM_PLACED) = range(9)
 NFEC_DGRAM_CLASSES = NFEC_DGRAM_PARSED = 9
+# nfec_rx_ingest_control / nfec_ctl_parse_host: a control datagram's class, the filter's flags
+(NFEC_CTL_UNREADABLE, NFEC_CTL_OTHER_TYPE, NFEC_CTL_MALFORMED, NFEC_CTL_OTHER_FLAVOR, NFEC_CTL_OWN, NFEC_CTL_OTHER_SENDER,
+ NFEC_CTL_OTHER_INSTANCE, NFEC_CTL_NACK, NFEC_CTL_REPAIR_ADV) = range(9)
+NFEC_CTL_CLASSES = 9
+NFEC_CTL_EXTENDED = 0x80
+NFEC_CTL_ANY_INSTANCE, NFEC_CTL_TAKE_NACK, NFEC_CTL_TAKE_ADV = 1, 2, 4
 NFEC_FEATURE_RS16_TOEPLITZ, NFEC_FEATURE_RS16_TOEPLITZ2 = 1, 2
 NFEC_OPT_RS16_SHARED_TABLES, NFEC_OPT_RS16_TOEPLITZ_OFF, NFEC_OPT_RS16_TOEPLITZ_ON, NFEC_OPT_HOST_ONLY = 1, 2, 4, 8
 NFEC_OPT_RS16_TOEPLITZ_ONE_LEVEL = 16
@@ -146,6 +152,45 @@ class DataFilter(ctypes.Structure):
         ("fec_id", ctypes.c_uint8),
         ("fec_m", ctypes.c_uint8),
         ("object_id", ctypes.c_uint16),
+    ]
+
+
+class NackHeader(ctypes.Structure):
+    """nfec_nack_header: the NORM_NACK header fields the messages of one call share."""
+    _fields_ = [
+        ("source_id", ctypes.c_uint32),
+        ("sender_id", ctypes.c_uint32),
+        ("instance_id", ctypes.c_uint16),
+        ("first_sequence", ctypes.c_uint16),
+        ("sequence_step", ctypes.c_uint16),
+        ("grtt_response_sec", ctypes.c_uint32),
+        ("grtt_response_usec", ctypes.c_uint32),
+        ("ext", ctypes.c_uint8 * 12),
+        ("ext_bytes", ctypes.c_uint8),
+    ]
+
+
+class AdvHeader(ctypes.Structure):
+    """nfec_adv_header: the header of one NORM_CMD(REPAIR_ADV)."""
+    _fields_ = [
+        ("source_id", ctypes.c_uint32),
+        ("instance_id", ctypes.c_uint16),
+        ("sequence", ctypes.c_uint16),
+        ("grtt", ctypes.c_uint8),
+        ("backoff", ctypes.c_uint8),
+        ("gsize", ctypes.c_uint8),
+        ("ext", ctypes.c_uint8 * 12),
+        ("ext_bytes", ctypes.c_uint8),
+    ]
+
+
+class CtlFilter(ctypes.Structure):
+    """nfec_ctl_filter: whose control messages one intake call takes."""
+    _fields_ = [
+        ("sender_id", ctypes.c_uint32),
+        ("instance_id", ctypes.c_uint16),
+        ("local_id", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
     ]
 
 
@@ -305,6 +350,17 @@ _SIGS = {
     "nfec_rx_parse_data_host": (_I, [ctypes.POINTER(DataFilter), _U32, _P, _U64, _P, _P, _U32, _P, _P, _P, _P, _P, _P, _P,
                                      _P]),
     "nfec_rx_data_chunks_host": (_I, [_U64, _U16, _P]),
+    "nfec_nack_header_bytes": (_I, [_U8]),
+    "nfec_adv_header_bytes": (_I, [_U8]),
+    "nfec_nack_fragment": (_I, [_P, _P, _U64, _P, _P, _U32, _U8, _U32, ctypes.POINTER(NackHeader), _P, _U64, _U32, _P, _P,
+                                _U32, _P, _P, _U64, _P]),
+    "nfec_nack_fragment_workspace_bytes": (_U64, [_U64, _U32]),
+    "nfec_tx_repair_adv_message": (_I, [_P, _P, _U64, _P, _U8, _U32, ctypes.POINTER(AdvHeader), _P, _U64, _P, _P, _P]),
+    "nfec_rx_ingest_control": (_I, [_P, ctypes.POINTER(RxMessages), ctypes.POINTER(CtlFilter), _P, _P, _P, _P, _P, _P, _P]),
+    "nfec_nack_fragment_host": (_I, [_P, _U64, _U8, _U32, ctypes.POINTER(NackHeader), _P, _U64, _U32, _P, _P, _U32, _P]),
+    "nfec_nack_header_write_host": (_I, [ctypes.POINTER(NackHeader), _U32, _P, ctypes.c_size_t]),
+    "nfec_adv_message_host": (_I, [_P, _U64, _U8, _U32, ctypes.POINTER(AdvHeader), _P, _U64, _P]),
+    "nfec_ctl_parse_host": (_I, [ctypes.POINTER(CtlFilter), _P, _U64, _P, _P, _U32, _P, _P, _P, _P, _P, _P]),
     "nfec_tx_handle_nacks": (_I, [_P, ctypes.POINTER(RxMessages), _U8, _U8, _U16, _U32, _P, _U32, _U32, _U32,
                                   ctypes.POINTER(TxRepairStateStruct), _U32, _P, _U64, _P, _P]),
     "nfec_tx_nack_workspace_bytes": (_U64, [_U32, _U32, _U32]),

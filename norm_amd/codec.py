@@ -483,6 +483,132 @@ class _Codec:
                                             _tensor_ptr(totals, "totals"), _stream_handle(stream)),
                 "nfec_rx_ingest_data")
 
+    # -- NORM_NACK and REPAIR_ADV messages on the device (nfec.h, "NORM_NACK and NORM_CMD(REPAIR_ADV) messages ...") --
+    def nack_messages(self, content, content_bytes_dev, header, segment_size, fec_id=5, block_start=None, wire=None,
+                      pitch=None, capacity=None, msg_offsets_out=None, msg_length_out=None, totals=None, workspace=None,
+                      stream=None):
+        """Repair-request content cut into whole NORM_NACK messages (nfec_nack_fragment).  content:
+        repair_requests' uint8 tensor; content_bytes_dev: its totals[:1] (a one-element int64 CUDA
+        tensor); block_start: repair_requests' second result, the hint that makes the request index
+        parallel, or None (correct, but one lane walks every request header).  header:
+        nack_header(...).  Message i lies at wire[i * pitch:]; pitch defaults to header +
+        segment_size, capacity to what `wire` holds or, with wire None, to what the content could
+        need.  Returns (wire uint8, msg_offsets int64 [capacity], msg_length int16 [capacity],
+        totals int64 [6] = (messages, content bytes written, requests read, requests split, content
+        bytes consumed, cut short)); totals[:1] is the count_dev of ingest_control and handle_nacks."""
+        import torch
+
+        self._need()
+        if content.element_size() != 1 or not content.is_cuda or not content.is_contiguous():
+            raise ValueError("content must be a contiguous uint8 CUDA (HIP) tensor")
+        if content_bytes_dev.element_size() != 8 or content_bytes_dev.numel() < 1 or not content_bytes_dev.is_cuda:
+            raise ValueError("content_bytes_dev must be a 64-bit CUDA (HIP) tensor")
+        dev = content.device
+        H = nack_header_bytes(header.ext_bytes)
+        pitch = H + segment_size if pitch is None else pitch
+        if wire is None:
+            if capacity is None:
+                capacity = content.numel() // max(segment_size - 64, 8) + 2
+            wire = torch.zeros(max(capacity * pitch, 4), dtype=torch.uint8, device=dev)
+        if capacity is None:
+            capacity = wire.numel() // pitch if pitch else 0
+        nb = 0
+        if block_start is not None:
+            if block_start.element_size() != 8 or block_start.dim() != 2 or block_start.shape[1] != 2:
+                raise ValueError("block_start must be a 64-bit tensor [nblocks + 1, 2]")
+            nb = block_start.shape[0] - 1
+        if msg_offsets_out is None:
+            msg_offsets_out = torch.zeros(capacity, dtype=torch.int64, device=dev)
+        if msg_length_out is None:
+            msg_length_out = torch.zeros(capacity, dtype=torch.int16, device=dev)
+        for t, size, what in ((msg_offsets_out, 8, "msg_offsets_out"), (msg_length_out, 2, "msg_length_out")):
+            if t.element_size() != size or t.numel() < capacity or not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous CUDA (HIP) tensor of {capacity} elements of {size} bytes")
+        if totals is None:
+            totals = torch.zeros(6, dtype=torch.int64, device=dev)
+        need = N.lib().nfec_nack_fragment_workspace_bytes(content.numel(), nb)
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        N.check(N.lib().nfec_nack_fragment(self._h, _tensor_ptr(content, "content"), content.numel(),
+                                           content_bytes_dev.data_ptr(), _tensor_ptr(block_start, "block_start"), nb,
+                                           fec_id, segment_size, ctypes.byref(header), _tensor_ptr(wire, "wire"),
+                                           wire.numel(), pitch, _tensor_ptr(msg_offsets_out, "msg_offsets_out"),
+                                           _tensor_ptr(msg_length_out, "msg_length_out"), capacity,
+                                           _tensor_ptr(totals, "totals"), _tensor_ptr(workspace, "workspace"),
+                                           workspace.numel(), _stream_handle(stream)), "nfec_nack_fragment")
+        return wire, msg_offsets_out, msg_length_out, totals
+
+    def repair_adv_message(self, content, content_bytes_dev, header, segment_size, fec_id=5, wire=None, stream=None):
+        """One NORM_CMD(REPAIR_ADV) from repair_adv's content (nfec_tx_repair_adv_message): the
+        header, then the first message of nack_messages' cut; the LIMIT flag is set when content
+        remained.  header: adv_header(...).  Returns (wire uint8, msg_length int16 [1], totals int64
+        [3] = (content bytes written, content bytes left out, limit flag))."""
+        import torch
+
+        self._need()
+        if content.element_size() != 1 or not content.is_cuda or not content.is_contiguous():
+            raise ValueError("content must be a contiguous uint8 CUDA (HIP) tensor")
+        if content_bytes_dev.element_size() != 8 or content_bytes_dev.numel() < 1 or not content_bytes_dev.is_cuda:
+            raise ValueError("content_bytes_dev must be a 64-bit CUDA (HIP) tensor")
+        dev = content.device
+        if wire is None:
+            wire = torch.zeros(adv_header_bytes(header.ext_bytes) + segment_size, dtype=torch.uint8, device=dev)
+        msg_length = torch.zeros(1, dtype=torch.int16, device=dev)
+        totals = torch.zeros(3, dtype=torch.int64, device=dev)
+        N.check(N.lib().nfec_tx_repair_adv_message(self._h, _tensor_ptr(content, "content"), content.numel(),
+                                                   content_bytes_dev.data_ptr(), fec_id, segment_size,
+                                                   ctypes.byref(header), _tensor_ptr(wire, "wire"), wire.numel(),
+                                                   _tensor_ptr(msg_length, "msg_length"), _tensor_ptr(totals, "totals"),
+                                                   _stream_handle(stream)), "nfec_tx_repair_adv_message")
+        return wire, msg_length, totals
+
+    def ingest_control(self, payloads, offsets, length, filter, count_dev=None, class_out=None, source_id_out=None,
+                       grtt_response_out=None, stats=None, stream=None):
+        """The intake for control datagrams (nfec_rx_ingest_control): offsets int64 / length int16
+        are each datagram's start and length in the wire buffer `payloads`; filter:
+        ctl_filter(...).  Returns (content_offset int64, content_length int16), index-aligned with
+        the datagrams: the arrays handle_nacks and handle_repair_content take with the same
+        payloads; a datagram that is not taken is the empty message (0, 0).  class_out uint8 /
+        source_id_out int32 / grtt_response_out int32 [count, 2]: tensors, or None.  stats: int32
+        [9], one counter per NFEC_CTL_* class (zero it first), or None."""
+        import torch
+
+        self._need()
+        count = offsets.numel()
+        given = [(offsets, 8, count, "offsets"), (length, 2, count, "length")]
+        given += [(t, size, n, what) for t, size, n, what in ((class_out, 1, count, "class_out"),
+                                                              (source_id_out, 4, count, "source_id_out"),
+                                                              (grtt_response_out, 4, 2 * count, "grtt_response_out"))
+                  if t is not None]
+        for t, size, n, what in given:
+            if t.element_size() != size or t.numel() != n:
+                raise ValueError(f"{what} must hold {n} elements of {size} bytes")
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous CUDA (HIP) tensor")
+        if stats is not None and (stats.element_size() != 4 or stats.numel() < N.NFEC_CTL_CLASSES):
+            raise ValueError("stats must hold nine 32-bit counters")
+        if count_dev is not None and (count_dev.element_size() != 8 or count_dev.numel() < 1 or not count_dev.is_cuda):
+            raise ValueError("count_dev must be a 64-bit CUDA (HIP) tensor")
+        if payloads.element_size() != 1 or not payloads.is_cuda or not payloads.is_contiguous():
+            raise ValueError("payloads must be a contiguous uint8 CUDA (HIP) tensor")
+        content_offset = torch.zeros(count, dtype=torch.int64, device=payloads.device)
+        content_length = torch.zeros(count, dtype=torch.int16, device=payloads.device)
+        msg = N.RxMessages()
+        msg.payloads = payloads.data_ptr() if payloads.numel() else None
+        msg.payload_bytes = payloads.numel()
+        msg.offsets, msg.length = offsets.data_ptr(), length.data_ptr()
+        msg.count = count
+        msg.count_dev = count_dev.data_ptr() if count_dev is not None else None
+        N.check(N.lib().nfec_rx_ingest_control(self._h, ctypes.byref(msg), ctypes.byref(filter),
+                                               _tensor_ptr(class_out, "class_out"),
+                                               _tensor_ptr(content_offset, "content_offset"),
+                                               _tensor_ptr(content_length, "content_length"),
+                                               _tensor_ptr(source_id_out, "source_id_out"),
+                                               _tensor_ptr(grtt_response_out, "grtt_response_out"),
+                                               _tensor_ptr(stats, "stats"), _stream_handle(stream)),
+                "nfec_rx_ingest_control")
+        return content_offset, content_length
+
     # -- sender repair state on the device (nfec.h, "sender repair state on the device") --
     def handle_nacks(self, state, payloads, offsets, length, num_data=None, fec_id=5, fec_m=8, object_id=0,
                      first_block_id=0, extra_parity=0, unit_capacity=None, count_dev=None, workspace=None,
@@ -1190,6 +1316,115 @@ def rx_data_chunks_host(off, length):
     out = (ctypes.c_uint64 * 3)()
     n = N.lib().nfec_rx_data_chunks_host(off, length, out)
     return [int(out[c]) for c in range(n)]
+
+
+def _ctl_ext(h, ext):
+    ext = bytes(ext) if ext is not None else b""
+    if len(ext) not in (0, 12):
+        raise ValueError("a CC-feedback extension has 12 bytes")
+    for j, v in enumerate(ext):
+        h.ext[j] = v
+    h.ext_bytes = len(ext)
+
+
+def nack_header(source_id, sender_id, instance_id, first_sequence=0, sequence_step=0, grtt_response=(0, 0), ext=None):
+    """nfec_nack_header: the fields the NORM_NACK messages of one nack_messages call share.
+    grtt_response: (seconds, microseconds); ext: the 12 bytes of a CC-feedback extension, or None.
+    sequence_step 0 gives every message first_sequence, as the reference sends its NACKs."""
+    h = N.NackHeader()
+    h.source_id, h.sender_id, h.instance_id = source_id & 0xFFFFFFFF, sender_id & 0xFFFFFFFF, instance_id & 0xFFFF
+    h.first_sequence, h.sequence_step = first_sequence & 0xFFFF, sequence_step & 0xFFFF
+    h.grtt_response_sec, h.grtt_response_usec = grtt_response[0] & 0xFFFFFFFF, grtt_response[1] & 0xFFFFFFFF
+    _ctl_ext(h, ext)
+    return h
+
+
+def adv_header(source_id, instance_id, sequence=0, grtt=0, backoff=0, gsize=0, ext=None):
+    """nfec_adv_header: the header of the NORM_CMD(REPAIR_ADV) repair_adv_message writes."""
+    h = N.AdvHeader()
+    h.source_id, h.instance_id, h.sequence = source_id & 0xFFFFFFFF, instance_id & 0xFFFF, sequence & 0xFFFF
+    h.grtt, h.backoff, h.gsize = grtt, backoff, gsize
+    _ctl_ext(h, ext)
+    return h
+
+
+def ctl_filter(sender_id, instance_id, local_id=0, flags=0):
+    """nfec_ctl_filter: whose control messages ingest_control / ctl_parse_host take.  flags:
+    NFEC_CTL_ANY_INSTANCE | NFEC_CTL_TAKE_NACK (a sender's intake) | NFEC_CTL_TAKE_ADV (a receiver's)."""
+    f = N.CtlFilter()
+    f.sender_id, f.instance_id, f.local_id, f.flags = sender_id & 0xFFFFFFFF, instance_id & 0xFFFF, local_id & 0xFFFFFFFF, flags
+    return f
+
+
+def nack_header_bytes(ext_bytes=0):
+    """nfec_nack_header_bytes: a NORM_NACK header's length, 24 or 36."""
+    return N.check(N.lib().nfec_nack_header_bytes(ext_bytes), "nfec_nack_header_bytes")
+
+
+def adv_header_bytes(ext_bytes=0):
+    """nfec_adv_header_bytes: a NORM_CMD(REPAIR_ADV) header's length, 16 or 28."""
+    return N.check(N.lib().nfec_adv_header_bytes(ext_bytes), "nfec_adv_header_bytes")
+
+
+def nack_header_write_host(header, i):
+    """nfec_nack_header_write_host: the header of message i of a call, as bytes."""
+    out = (ctypes.c_uint8 * 36)()
+    n = N.check(N.lib().nfec_nack_header_write_host(ctypes.byref(header), i & 0xFFFFFFFF, out, 36),
+                "nfec_nack_header_write_host")
+    return bytes(out[:n])
+
+
+def nack_fragment_host(content, header, segment_size, fec_id=5, pitch=None, capacity=None):
+    """nfec_nack_fragment_host: Codec.nack_messages on a host array (no GPU): (wire uint8 [capacity
+    * pitch], msg_offsets uint64 [capacity], msg_length uint16 [capacity], totals uint64 [6]).
+    capacity defaults to what the content could need."""
+    import numpy as np
+
+    content = np.ascontiguousarray(content, np.uint8)
+    H = nack_header_bytes(header.ext_bytes)
+    pitch = H + segment_size if pitch is None else pitch
+    if capacity is None:
+        capacity = content.size // 8 + 2
+    wire = np.zeros(capacity * pitch, np.uint8)
+    offs, lens = np.zeros(capacity, np.uint64), np.zeros(capacity, np.uint16)
+    totals = np.zeros(6, np.uint64)
+    N.check(N.lib().nfec_nack_fragment_host(content.ctypes.data, content.size, fec_id, segment_size, ctypes.byref(header),
+                                            wire.ctypes.data, wire.size, pitch, offs.ctypes.data, lens.ctypes.data,
+                                            capacity, totals.ctypes.data), "nfec_nack_fragment_host")
+    return wire, offs, lens, totals
+
+
+def adv_message_host(content, header, segment_size, fec_id=5):
+    """nfec_adv_message_host: Codec.repair_adv_message on a host array (no GPU): (message bytes,
+    totals uint64 [3])."""
+    import numpy as np
+
+    content = np.ascontiguousarray(content, np.uint8)
+    wire = np.zeros(adv_header_bytes(header.ext_bytes) + segment_size, np.uint8)
+    totals = np.zeros(3, np.uint64)
+    n = N.check(N.lib().nfec_adv_message_host(content.ctypes.data, content.size, fec_id, segment_size,
+                                              ctypes.byref(header), wire.ctypes.data, wire.size, totals.ctypes.data),
+                "nfec_adv_message_host")
+    return wire[:n].tobytes(), totals
+
+
+def ctl_parse_host(filter, wire, offsets, length):
+    """nfec_ctl_parse_host: Codec.ingest_control on host arrays (no GPU): (class uint8,
+    content_offset uint64, content_length uint16, source_id uint32, grtt_response uint32 [count, 2],
+    stats uint32 [9]).  wire: uint8 array; offsets uint64 / length uint16: each datagram's start and
+    length."""
+    import numpy as np
+
+    wire = np.ascontiguousarray(wire, np.uint8)
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    length = np.ascontiguousarray(length, np.uint16)
+    n = offsets.size
+    cls, coff, clen = np.zeros(n, np.uint8), np.zeros(n, np.uint64), np.zeros(n, np.uint16)
+    src, grtt, stats = np.zeros(n, np.uint32), np.zeros((n, 2), np.uint32), np.zeros(9, np.uint32)
+    N.check(N.lib().nfec_ctl_parse_host(ctypes.byref(filter), wire.ctypes.data, wire.size, offsets.ctypes.data,
+                                        length.ctypes.data, n, cls.ctypes.data, coff.ctypes.data, clen.ctypes.data,
+                                        src.ctypes.data, grtt.ctypes.data, stats.ctypes.data), "nfec_ctl_parse_host")
+    return cls, coff, clen, src, grtt, stats
 
 
 def repair_max_units(fec_id):

@@ -1235,6 +1235,111 @@ int nfec_rx_ingest_data(const nfec_codec* codec, const nfec_block_batch* batch, 
     return launch_rx_ingest_data(a, static_cast<hipStream_t>(stream));
 }
 
+// ---- NORM_NACK and NORM_CMD(REPAIR_ADV) messages on the device (kernels_ctlmsg.hip) ----
+uint64_t nfec_nack_fragment_workspace_bytes(uint64_t content_capacity, uint32_t nblocks)
+{
+    return nack_fragment_workspace(content_capacity, nblocks);
+}
+
+int nfec_nack_fragment(const nfec_codec* codec, const void* content, uint64_t content_capacity,
+                       const uint64_t* content_bytes_dev, const uint64_t* block_start, uint32_t nblocks, uint8_t fec_id,
+                       uint32_t segment_size, const nfec_nack_header* header, void* wire, uint64_t wire_bytes, uint32_t pitch,
+                       uint64_t* msg_offsets_out, uint16_t* msg_length_out, uint32_t capacity, uint64_t* totals,
+                       void* workspace, uint64_t workspace_bytes, void* stream)
+{
+    if (!codec) return fail(NFEC_EINVAL, "null codec");
+    NackFragmentArgs a;
+    int rc = nack_header_fixed_from(header, a.header);
+    if (rc || (rc = cut_params_from(fec_id, segment_size, a.header.hdr_bytes, a.cut, "nack_fragment"))) return rc;
+    if (!content || !content_bytes_dev || !totals) return fail(NFEC_EINVAL, "nack_fragment: null content, content_bytes_dev or totals");
+    if (reinterpret_cast<uintptr_t>(content) & 3u) return fail(NFEC_EINVAL, "nack_fragment: content is not 4-byte aligned");
+    if (content_capacity >> 32) return fail(NFEC_ERANGE, "nack_fragment: content_capacity of 2^32 or more");
+    if (!block_start && nblocks) return fail(NFEC_EINVAL, "nack_fragment: null block_start with nblocks > 0");
+    if ((pitch & 3u) || pitch < a.header.hdr_bytes + a.cut.S)
+        return fail(NFEC_EINVAL, "nack_fragment: pitch is no multiple of 4 or below header + segment_size");
+    if (capacity && (!wire || (reinterpret_cast<uintptr_t>(wire) & 3u)))
+        return fail(NFEC_EINVAL, "nack_fragment: wire is null or not 4-byte aligned");
+    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 7u) ||
+        workspace_bytes < nack_fragment_workspace(content_capacity, block_start ? nblocks : 0))
+        return fail(NFEC_EINVAL, "nack_fragment: workspace is null, not 8-byte aligned or below nfec_nack_fragment_workspace_bytes");
+    if (primary(codec)->host_only) return host_only_fail();
+    const nfec_codec* c = stripe_for(const_cast<nfec_codec*>(codec), content);
+    if (!c) return fail(NFEC_EINVAL, "content is not on a device of the codec");
+    DeviceGuard g(c->device);
+    a.content = static_cast<const uint32_t*>(content);
+    a.content_capacity = content_capacity;
+    a.content_bytes_dev = content_bytes_dev;
+    a.block_start = block_start;
+    a.nblocks = block_start ? nblocks : 0;
+    a.wire = static_cast<uint8_t*>(wire);
+    a.pitch = pitch;
+    a.msg_offsets_out = msg_offsets_out;
+    a.msg_length_out = msg_length_out;
+    a.capacity = (uint32_t)std::min<uint64_t>(capacity, wire_bytes / pitch);
+    a.totals = totals;
+    a.workspace = static_cast<uint8_t*>(workspace);
+    return launch_nack_fragment(a, static_cast<hipStream_t>(stream));
+}
+
+int nfec_tx_repair_adv_message(const nfec_codec* codec, const void* content, uint64_t content_capacity,
+                               const uint64_t* content_bytes_dev, uint8_t fec_id, uint32_t segment_size,
+                               const nfec_adv_header* header, void* wire, uint64_t wire_bytes, uint16_t* msg_length_out,
+                               uint64_t* totals, void* stream)
+{
+    if (!codec) return fail(NFEC_EINVAL, "null codec");
+    AdvMessageArgs a;
+    int rc = adv_header_fixed_from(header, a.header);
+    if (rc || (rc = cut_params_from(fec_id, segment_size, a.header.hdr_bytes, a.cut, "tx_repair_adv_message"))) return rc;
+    if (!content || !content_bytes_dev || !totals || !msg_length_out)
+        return fail(NFEC_EINVAL, "tx_repair_adv_message: null content, content_bytes_dev, msg_length_out or totals");
+    if (reinterpret_cast<uintptr_t>(content) & 3u) return fail(NFEC_EINVAL, "tx_repair_adv_message: content is not 4-byte aligned");
+    if (content_capacity >> 32) return fail(NFEC_ERANGE, "tx_repair_adv_message: content_capacity of 2^32 or more");
+    if (!wire || (reinterpret_cast<uintptr_t>(wire) & 3u) || wire_bytes < (uint64_t)a.header.hdr_bytes + a.cut.S)
+        return fail(NFEC_EINVAL, "tx_repair_adv_message: wire is null, not 4-byte aligned or below header + segment_size");
+    if (primary(codec)->host_only) return host_only_fail();
+    const nfec_codec* c = stripe_for(const_cast<nfec_codec*>(codec), content);
+    if (!c) return fail(NFEC_EINVAL, "content is not on a device of the codec");
+    DeviceGuard g(c->device);
+    a.content = static_cast<const uint32_t*>(content);
+    a.content_capacity = content_capacity;
+    a.content_bytes_dev = content_bytes_dev;
+    a.wire = static_cast<uint32_t*>(wire);
+    a.msg_length_out = msg_length_out;
+    a.totals = totals;
+    return launch_adv_message(a, static_cast<hipStream_t>(stream));
+}
+
+int nfec_rx_ingest_control(const nfec_codec* codec, const nfec_rx_messages* msg, const nfec_ctl_filter* filter, uint8_t* class_out,
+                           uint64_t* content_offset_out, uint16_t* content_length_out, uint32_t* source_id_out,
+                           uint32_t* grtt_response_out, uint32_t* stats, void* stream)
+{
+    if (!codec || !msg) return fail(NFEC_EINVAL, "null codec or datagrams");
+    CtlIngestArgs a;
+    int rc = ctl_filter_from(filter, a.filter);
+    if (rc) return rc;
+    if (msg->count && (!msg->payloads || !msg->offsets || !msg->length)) return fail(NFEC_EINVAL, "null datagrams array");
+    if (msg->count && (!content_offset_out || !content_length_out))
+        return fail(NFEC_EINVAL, "rx_ingest_control: null content_offset_out or content_length_out");
+    if (primary(codec)->host_only) return host_only_fail();
+    if (msg->count == 0) return NFEC_OK;
+    const nfec_codec* c = stripe_for(const_cast<nfec_codec*>(codec), msg->payloads);
+    if (!c) return fail(NFEC_EINVAL, "wire buffer is not on a device of the codec");
+    DeviceGuard g(c->device);
+    a.payloads = static_cast<const uint8_t*>(msg->payloads);
+    a.payload_bytes = msg->payload_bytes;
+    a.offsets = msg->offsets;
+    a.length = msg->length;
+    a.count = msg->count;
+    a.count_dev = msg->count_dev;
+    a.class_out = class_out;
+    a.content_offset_out = content_offset_out;
+    a.content_length_out = content_length_out;
+    a.source_id_out = source_id_out;
+    a.grtt_response_out = grtt_response_out;
+    a.stats = stats;
+    return launch_ctl_ingest(a, static_cast<hipStream_t>(stream));
+}
+
 // ---- object segmentation on the device (kernels_obj.hip) ----
 // Arguments first, then the codec's device, as above.  The layout is taken only as
 // nfec_object_layout_for makes it: the kernels index the object and the batch by its fields, so a

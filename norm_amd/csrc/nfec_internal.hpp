@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/nfec.h"
+#include "ctl_msg.hpp"
 #include "data_msg.hpp"
 
 namespace nfec {
@@ -867,6 +868,62 @@ int launch_rx_ingest_data(const RxIngestDataArgs& a, hipStream_t s);
 // the caller's structs into the kernels' constants, with the checks the host twins share (data_msg_host.cpp)
 int data_header_fixed_from(const nfec_data_header* h, DataHeaderFixed& f);
 int data_filter_from(const nfec_data_filter* in, DataFilter& f);
+
+// NORM_NACK and NORM_CMD(REPAIR_ADV) messages on the device (kernels_ctlmsg.hip; nfec.h "NORM_NACK and
+// NORM_CMD(REPAIR_ADV) messages on the device"; ctl_msg.hpp holds the headers, the cut and the parse).
+// Fragment: the request index (count per stretch of the hint, scan, write), the table of next states
+// over the content's dwords and its 64th power by doubling, one workgroup that numbers the messages,
+// one wave per message that writes it.
+struct NackFragmentArgs {
+    const uint32_t* content = nullptr;     // 4-byte aligned
+    uint64_t content_capacity = 0;         // < 2^32
+    const uint64_t* content_bytes_dev = nullptr;
+    const uint64_t* block_start = nullptr; // [nblocks + 1][2], or null with nblocks 0
+    uint32_t nblocks = 0;
+    CutParams cut;
+    CtlHeaderFixed header;
+    uint8_t* wire = nullptr;               // 4-byte aligned
+    uint32_t pitch = 0;
+    uint64_t* msg_offsets_out = nullptr;   // [capacity], or null
+    uint16_t* msg_length_out = nullptr;    // [capacity], or null
+    uint32_t capacity = 0;                 // min(the caller's, wire_bytes / pitch)
+    uint64_t* totals = nullptr;            // [6]
+    uint8_t* workspace = nullptr;
+};
+uint64_t nack_fragment_workspace(uint64_t content_capacity, uint32_t nblocks);
+int launch_nack_fragment(const NackFragmentArgs& a, hipStream_t s);
+struct AdvMessageArgs {
+    const uint32_t* content = nullptr;
+    uint64_t content_capacity = 0;
+    const uint64_t* content_bytes_dev = nullptr;
+    CutParams cut;
+    CtlHeaderFixed header;
+    uint32_t* wire = nullptr;              // 4-byte aligned, H + S bytes at least
+    uint16_t* msg_length_out = nullptr;    // [1]
+    uint64_t* totals = nullptr;            // [3]
+};
+int launch_adv_message(const AdvMessageArgs& a, hipStream_t s);
+struct CtlIngestArgs {
+    const uint8_t* payloads = nullptr;
+    uint64_t payload_bytes = 0;
+    const uint64_t* offsets = nullptr;
+    const uint16_t* length = nullptr;
+    uint32_t count = 0;
+    const uint64_t* count_dev = nullptr;
+    CtlFilter filter;
+    uint8_t* class_out = nullptr;          // [count], or null
+    uint64_t* content_offset_out = nullptr;  // [count]
+    uint16_t* content_length_out = nullptr;  // [count]
+    uint32_t* source_id_out = nullptr;     // [count], or null
+    uint32_t* grtt_response_out = nullptr; // [count][2], or null
+    uint32_t* stats = nullptr;             // [9], or null
+};
+int launch_ctl_ingest(const CtlIngestArgs& a, hipStream_t s);
+// the caller's structs into the kernels' constants, with the checks the host twins share (ctl_msg_host.cpp)
+int nack_header_fixed_from(const nfec_nack_header* h, CtlHeaderFixed& f);
+int adv_header_fixed_from(const nfec_adv_header* h, CtlHeaderFixed& f);
+int ctl_filter_from(const nfec_ctl_filter* in, CtlFilter& f);
+int cut_params_from(uint8_t fec_id, uint32_t segment_size, uint32_t hdr_bytes, CutParams& c, const char* what);
 
 // Repair requests on the device (kernels_nack.hip; nfec.h "repair requests on the device").  The
 // shape of the transmission list: per-block classes, bytes and requests (one wave per block) into
